@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Headline benchmark: Chebyshev ``prop_step!``/s on BASELINE.json's configs.
 
-    python bench.py                      # = --gpus 1 --steps 100 --warmup 10: config C2, a few minutes with
-                                         #   the PMC passes, the CPU baselines and the extra points
+    python bench.py                      # = --gpus 1 --steps 100 --warmup 10: config C2, the headline alone
+    python bench.py --full               # the same line with the CPU baselines, the PMC passes and the extra points: a few minutes
+    python bench.py --dump-outputs DIR   # also writes the state after the last timed step to DIR/psi.npy (float64, [re, im])
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -412,6 +413,31 @@ def emit(full, tag=""):
     sys.stdout.flush()
 
 
+DUMP_BYTES = 48 << 20      # --dump-outputs: bytes of the files one run writes, all ranks together (the outputs stay below 64 MB)
+NPY_HEADER_BYTES = 4096    # what is kept back from the budget for the headers of the .npy files of one dump_outputs call
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: each array as dirname/<name>.npy in float64, a complex one with a trailing (re, im) axis; the files of
+    one call take at most `budget` bytes.  An array that does not fit is written as a fixed, seeded sample of its rows, whose
+    row numbers go to <name>_rows.npy (8 bytes per kept row, counted in the budget)."""
+    os.makedirs(dirname, exist_ok=True)
+    left = budget - NPY_HEADER_BYTES
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if np.iscomplexobj(a):
+            a = np.stack([a.real, a.imag], axis=-1)
+        a = a.astype(np.float64, copy=False)
+        if a.nbytes > left:
+            k = max(left, 0) // (a.nbytes // a.shape[0] + 8)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], k, replace=False))
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+            left -= 8 * k
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def run_c5(args, world, rank, local_rank, one_gpu, dist, L, synth, bp):
     """BASELINE configs[4]: 64 states x N = 2^18 CSR H, Chebyshev on the panel, the batch split over the GPUs --
     rank r advances states [r b, (r + 1) b), b = 64 / world, with its own copy of H and no communication (SURVEY 8e
@@ -447,6 +473,8 @@ def run_c5(args, world, rank, local_rank, one_gpu, dist, L, synth, bp):
     ev_ms = ctx.timer_end()
     barrier()
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"panel" + (f"_rank{rank}" if world > 1 else ""): bs.local_states()}, DUMP_BYTES // world)
     norms = np.linalg.norm(bs.local_states(), axis=0)
     drift = float(np.max(np.abs(norms - 1.0)))
     if dist is not None:
@@ -536,17 +564,30 @@ def main():
                     help="N > 1: boundary/interior overlap of the exchange, the exchange in line, or whichever a short trial finds faster")
     ap.add_argument("--driver", default="native", choices=["native", "torch"],
                     help="multi-GPU step: one library call with its own RCCL communicator, or the Python loop")
-    ap.add_argument("--cpu-steps", type=int, default=16,
-                    help="steps of the CPU baseline sample (0 = skip); 16 steps ~ 10 s of one core (c5: per sampled state, 4 states)")
-    ap.add_argument("--no-pmc", action="store_true", help="do not measure roofline.traffic with rocprofv3 child runs")
-    ap.add_argument("--no-extras", action="store_true", help="headline only: no extra points (formats, patterns, C3, C5)")
-    ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the strong-scaling point")
-    ap.add_argument("--no-allgather", action="store_true", help="N > 1: skip the 4-step measurement of the all-gather exchange form")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: CPU baselines, roofline.traffic from rocprofv3 child runs, the HBM stream "
+                         "yardsticks, the extra points (formats, patterns, sizes, C3, C5) and, N > 1, the strong-scaling and all-gather "
+                         "points; without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the state, or the panel) to DIR/<name>.npy as float64")
+    ap.add_argument("--cpu-steps", type=int, default=None,
+                    help="steps of the CPU baseline sample (0 = skip; default 16 with --full, else 0); 16 steps ~ 10 s of one core "
+                         "(c5: per sampled state, 4 states)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: do not measure roofline.traffic with rocprofv3 child runs")
+    ap.add_argument("--no-extras", action="store_true", help="--full: no extra points (formats, patterns, C3, C5)")
+    ap.add_argument("--no-strong", action="store_true", help="--full, N > 1: skip the strong-scaling point")
+    ap.add_argument("--no-allgather", action="store_true", help="--full, N > 1: skip the 4-step measurement of the all-gather exchange form")
     ap.add_argument("--no-safe", action="store_true", help="N > 1: skip the conservative first measurement and the watchdog")
     ap.add_argument("--point", default=None, choices=["c3", "c5"], help=argparse.SUPPRESS)      # one extras point only (PMC child runs)
     ap.add_argument("--watchdog", type=float, default=float(os.environ.get("QP_BENCH_WATCHDOG", "420")),
                     help="N > 1: seconds the native / overlapped path (set-up, self-check, trial, measurement, strong point) may take")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.cpu_steps is None:
+        args.cpu_steps = 16 if args.full else 0
+    if not args.full:
+        args.no_pmc = args.no_extras = args.no_strong = args.no_allgather = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1107,6 +1148,9 @@ def main():
     else:
         strong = None
         elapsed, ev_ms, st = timed_steps(step)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"psi" + (f"_rank{rank}" if world > 1 else ""): psi.numpy() if world == 1 else sh.local_state()},
+                     DUMP_BYTES // world)
 
     # ---- single GPU: CPU baselines, HBM traffic measured under rocprofv3, the other points ------------
     traffic = traffic_src = traffic_detail = None

@@ -2,10 +2,10 @@
 """Extract, from the reference's Julia sources, the signatures the Julia glue (julia/QuantumPropagatorsHIPExt.jl) relies
 on: every method of the helper functions it imports (positional arity range, keyword names, varargs), the fields of the
 structs it reads, the public property names of a propagator, and where each lives (file:line).  Written as DATA
-(tests/golden/reference_api.json); tests/test_julia_glue_signatures.py checks the glue against it, and -- where
-/root/reference is present -- that the file is what this script produces from the sources there.
+(tests/golden/reference_api.json); tests/test_julia_glue_signatures.py checks the glue against it.  Run again on a
+checkout of the reference whenever the reference changes:
 
-    python tests/golden/make_reference_api.py [/root/reference]
+    python tests/golden/make_reference_api.py <checkout of QuantumPropagators.jl>
 """
 import json
 import os
@@ -121,8 +121,9 @@ def scan(ref):
 
 
 def main():
-    ref = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
-    api = scan(ref)
+    if len(sys.argv) != 2:
+        sys.exit(__doc__)
+    api = scan(sys.argv[1])
     with open(OUT, "w") as f:
         json.dump(api, f, indent=1, sort_keys=True)
         f.write("\n")

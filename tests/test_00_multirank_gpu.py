@@ -148,7 +148,7 @@ def test_bench_eight_ranks_full_c4_flow_one_gpu():
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0", QP_BENCH_ONE_GPU="1")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2",
-                                       "--warmup", "1"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+                                       "--warmup", "1", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for p in procs:
         try:
@@ -260,7 +260,7 @@ def test_bench_multirank_flow_one_gpu(world, driver):
     """bench.py as the driver launches it for N > 1, in its test mode where the ranks share GPU 0 and the exchange is staged
     through the host: partition, self-check of the native step against the torch-driven one, barrier + max over ranks, one
     JSON line from rank 0 with the whole-job value, the complete record in the sidecar."""
-    d, full, _ = _bench(world, ["--steps", "3", "--warmup", "1", "--log2n", "16", "--driver", driver], timeout=240)
+    d, full, _ = _bench(world, ["--steps", "3", "--warmup", "1", "--log2n", "16", "--driver", driver, "--full"], timeout=240)
     assert d["extras_file"] == f"bench_extras_c4_gpus{world}_n16.json"
     assert d["degraded"] is False and d["native_path"].startswith("ok")
     assert d["n_gpus"] == world and d["steps"] == 3 and d["warmup"] == 1 and d["scaling"] == "weak"
@@ -335,13 +335,14 @@ def test_bench_c5_batch_split_flow_one_gpu(world):
     assert d["roofline"]["kernel"] == ("csr_spmm_kernel" if 64 // world <= 32 else "spmm_tile_kernel")      # (the lattice's interior rows in LDS-staged tiles)
     if world == 1:
         assert full["config"]["lds_tiles"]["taken"] == 1 and full["config"]["lds_tiles"]["tiles"] * 16 + full["config"]["lds_tiles"]["rest_rows"] == 1 << 14
-    assert d["cpu_baseline"] is None                    # --cpu-steps 0; the default run of `--config c5` carries one (test below)
+    assert d["cpu_baseline"] is None                    # --cpu-steps 0; `--config c5 --full` carries one (test below)
 
 
 def test_bench_c5_line_carries_a_cpu_baseline():
     """`bench.py --config c5` on one GPU (small size): `cpu_baseline` = oracle/cheby_ref.c on a sample of the panel's states
     (same H, same coefficients, serial CSC path), in the line's unit, and the sampled states of the GPU panel agree with it."""
-    d, full, _ = _bench(1, ["--config", "c5", "--steps", "2", "--warmup", "1", "--log2n", "14", "--cpu-steps", "2", "--no-pmc"], timeout=300)
+    d, full, _ = _bench(1, ["--config", "c5", "--steps", "2", "--warmup", "1", "--log2n", "14", "--cpu-steps", "2", "--no-pmc", "--full"],
+                        timeout=300)
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] == 1 and cb["unit"] == "state_step/s" and cb["value"] > 0
     assert cb["l2_diff_vs_gpu_after_sample"] < 1e-10 and "states" in cb["sample"]
@@ -393,7 +394,7 @@ def test_bench_single_gpu_line_is_physical():
     """bench.py on one GPU (small size): `roofline.frac` prices the shipped layout's bytes and stays below 1, the
     contract's CSR figure is reported separately, and `traffic` is measured in the run (child processes under
     rocprofv3 --pmc), not read from a file."""
-    d, full, _ = _bench(1, ["--steps", "5", "--warmup", "1", "--cpu-steps", "0", "--log2n", "17", "--no-extras"], timeout=900)
+    d, full, _ = _bench(1, ["--steps", "5", "--warmup", "1", "--cpu-steps", "0", "--log2n", "17", "--no-extras", "--full"], timeout=900)
     assert d["extras_file"] == "bench_extras_c2_n17.json"
     rf = full["roofline"]
     assert d["n_gpus"] == 1 and d["config"]["N_total"] == 1 << 17
@@ -421,6 +422,34 @@ def test_bench_config_c4_on_one_gpu_is_the_fixed_problem():
     rf = full["roofline"]
     assert len(rf["launch_us_segments"]) == 4 and rf["unstable"] in (False, True) and 0 < rf["frac"] <= 1.0
     assert list(d["roofline"])[:8] == ["bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "avg_launch_us"]     # the gate scalars lead
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_state(tmp_path):
+    """`bench.py` without `--full`, at the headline config (where `--full` adds the extra points, the CPU baselines, the PMC passes
+    and the stream yardsticks), measures the headline and nothing else, times exactly --steps steps, and `--dump-outputs DIR`
+    writes the state after the last timed step: the oracle's state after warmup + steps prop_steps from the same seeded input."""
+    sys.path.insert(0, ROOT)
+    import qprop_amd.synth as synth
+    from oracle import qp_oracle as qo
+    warmup, steps = 2, 3
+    d, full, _ = _bench(1, ["--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path)], timeout=300)
+    assert d["extras_file"] == "bench_extras.json" and d["config"]["N_total"] == 1 << 20       # the default run, the headline config
+    assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-4 * d["value"]
+    assert d["cpu_baseline"] is None and "points" not in d and full["extras"] is None and full["cpu_baseline_all_cores"] is None
+    rf = full["roofline"]
+    assert rf["traffic_source"].startswith("STATIC") and d["roofline"]["traffic_measured"] is False     # no rocprofv3 child runs
+    assert rf["stream_read_gbs"] is None and rf["hbm_resident_frac"] is None
+    N = 1 << 20
+    got = np.load(tmp_path / "psi.npy")
+    assert got.dtype == np.float64 and got.shape == (N, 2) and sorted(os.listdir(tmp_path)) == ["psi.npy"]
+    rp, col, vals = synth.hermitian_offsets_csr(N, offsets=synth.BANDED_OFFSETS)
+    H = synth.to_scipy(rp, col, vals, N)
+    psi = synth.random_state(N, row_begin=0, row_end=N)
+    wrk = qo.ChebyWrk(psi, 20.0, -10.0, 1.0)
+    for _ in range(warmup + steps):
+        psi = qo.cheby(psi, H, 1.0, wrk)
+    assert np.linalg.norm(got[:, 0] + 1j * got[:, 1] - psi) < 1e-10
 
 
 def test_bench_extras_points_are_physical():

@@ -245,3 +245,22 @@ def test_printed_line_of_a_multi_gpu_and_a_c5_record_stays_under_the_limit(capsy
     b.emit(full)
     line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
     assert "points" not in line and line["roofline"]["frac"] > 0 and len(json.dumps(line, separators=(",", ":"))) < 4096
+
+
+def test_dumped_outputs_are_float64_and_a_large_array_a_fixed_sample_of_its_rows(tmp_path):
+    b = _bench()
+    z = np.arange(4096, dtype=np.float64) * (1 + 2j)
+    b.dump_outputs(str(tmp_path / "small"), {"psi": z})
+    got = np.load(tmp_path / "small" / "psi.npy")
+    assert got.dtype == np.float64 and got.shape == (4096, 2) and np.array_equal(got[:, 0] + 1j * got[:, 1], z)
+    budget = 1 << 16
+    for name, big in (("panel", (np.arange(4096 * 8) * (1 - 1j)).reshape(4096, 8)), ("psi", np.arange(1 << 16) * (1 - 1j))):
+        for d in ("a", "b"):      # over the budget: the same seeded rows every time, in order
+            b.dump_outputs(str(tmp_path / name / d), {name: big}, budget=budget)
+        rows = np.load(tmp_path / name / "a" / f"{name}_rows.npy")
+        part = np.load(tmp_path / name / "a" / f"{name}.npy")
+        assert rows.dtype == np.float64 and np.array_equal(rows, np.load(tmp_path / name / "b" / f"{name}_rows.npy"))
+        assert np.all(np.diff(rows) > 0) and np.array_equal(part[..., 0] + 1j * part[..., 1], big[rows.astype(np.int64)])
+        # everything written -- the sample, its row numbers and both headers -- within the budget, and most of it used
+        written = sum(f.stat().st_size for f in (tmp_path / name / "a").iterdir())
+        assert budget // 2 < written <= budget, (name, written)

@@ -195,7 +195,6 @@ def test_destructors_named_in_handles_exist():
 
 # ---- the reference side of the glue: imported helpers, struct fields, the propagator contract ---------------------
 API = os.path.join(ROOT, "tests", "golden", "reference_api.json")
-REFERENCE = "/root/reference"
 
 
 def _glue_code():
@@ -230,19 +229,6 @@ def _calls_of(name, txt):
         splat = any(a.endswith("...") for a in pos)
         out.append((None if splat else len(pos), kws, txt[:m.start()].count("\n") + 1))
     return out
-
-
-def test_reference_api_fixture_is_current():
-    """tests/golden/reference_api.json is what make_reference_api.py extracts from the reference (checked where the
-    reference is present: this container; the GPU box only has the committed file)."""
-    import pytest
-    if not os.path.isdir(os.path.join(REFERENCE, "src")):
-        pytest.skip("the reference sources are not on this machine")
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("make_reference_api", os.path.join(ROOT, "tests", "golden", "make_reference_api.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    assert json.loads(json.dumps(mod.scan(REFERENCE), sort_keys=True)) == json.load(open(API))
 
 
 def test_helpers_imported_from_the_reference_exist_with_the_arity_used():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/rNN/single_gpu_sizes.json from a single-GPU bench line: the per-term times at 2^20 ... 2^24 rows that a
+"""profiles/rNN/single_gpu_sizes.json from the record of a single-GPU `bench.py --full` run: the per-term times at 2^20 ... 2^24 rows that a
 multi-GPU line's `scaling_prediction` is built from when the run itself cannot measure them (bench.py: STATIC_SIZES).
 
     python tools/make_single_gpu_sizes.py gpurun_out/r4/bench_line.json profiles/r04/single_gpu_sizes.json
