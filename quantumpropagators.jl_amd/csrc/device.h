@@ -3,7 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "qprop_internal.h"
+#include "layout_constants.h"
 
 namespace qp {
 
@@ -17,7 +17,6 @@ namespace qp {
     }                                                                                        \
   } while (0)
 
-constexpr int kRB = 64;           // rows per row block = one wavefront
 constexpr int kRedBlocks = 256;   // fixed grid of the reduction kernels (deterministic order)
 constexpr int kThreads = 256;
 
@@ -134,7 +133,7 @@ struct ColBlockPlan {
 // content shared between blocks.  The mat-vec kernels read the COMBINED table tab[(tptr[b] >> 9) + code] = sum_l c_l tuple_l: the
 // same arithmetic on the same numbers as the value plane they replace (bit-identical results), 1 B + a cached table line per
 // entry instead of 16 B.  evaluate! (src/generators.jl:757-766) recombines the tables IN ADDITION to the value plane (operator_refresh,
-// engine_core.hip): the plane stays the source of truth for the consumers that read it (Arnoldi mat-vecs without a dictionary path,
+// engine_operator.hip): the plane stays the source of truth for the consumers that read it (Arnoldi mat-vecs without a dictionary path,
 // the panel kernels, qp_operator_get_csr, the split), so the mirror saves bytes per mat-vec, not work per evaluate!.
 struct CodedVals {
   int valid = 0;
@@ -275,8 +274,6 @@ int launch_colblock_cheby(hipStream_t s, const DevMatrix& A, const double2* x, c
 int launch_colblock_plain(hipStream_t s, const DevMatrix& A, const double2* x, const PlainEpi& e, const Tuning& tun, bool* launched);
 // vals[p] = src[map[p]] (conjugated for a negative map entry); real != NULL: also real[p] = Re vals[p]
 int launch_colblock_gather(hipStream_t s, const ColBlockPlan& P, const double2* src, Stats* st);
-// the formats whose value array is in CSR order (rowptr / cols / vals[p])
-inline bool csr_layout(int format) { return format == QP_FMT_CSR || format == QP_FMT_DENSE; }
 int spmv_grid_size(const DevMatrix& A);
 // dense row-sum kernel (kernels_dense.hip): rows per wavefront and the grid that follows from it -- shared with spmv_grid_size,
 // which sizes the per-workgroup partials of check_normalization

@@ -11,6 +11,7 @@
 #include <memory>
 
 #include "device.h"
+#include "operator_layout.h"
 
 using qp::cplx;
 using qp::DevMatrix;
@@ -48,45 +49,12 @@ struct qp_state {
   bool own;
 };
 
-// Host arrays of the size of a matrix (gigabytes at N = 2^24): resize() leaves the new elements unwritten -- whoever resizes fills them,
-// on several threads -- instead of one thread zeroing them first (std::vector<T>: a serial pass over memory before the real one)
-namespace qp {
-template <class T>
-struct NoInitAlloc {
-  using value_type = T;
-  NoInitAlloc() = default;
-  template <class U>
-  NoInitAlloc(const NoInitAlloc<U>&) {}
-  T* allocate(size_t n) { return static_cast<T*>(::operator new(n * sizeof(T))); }
-  void deallocate(T* p, size_t) { ::operator delete(p); }
-  template <class U, class... A>
-  void construct(U* p, A&&... a) {
-    if constexpr (sizeof...(A) > 0) ::new ((void*)p) U(std::forward<A>(a)...);      // (no arguments: nothing written)
-  }
-  template <class U>
-  bool operator==(const NoInitAlloc<U>&) const { return true; }
-  template <class U>
-  bool operator!=(const NoInitAlloc<U>&) const { return false; }
-};
-template <class T>
-using HostVec = std::vector<T, NoInitAlloc<T>>;
-}  // namespace qp
-
 struct qp_matrix {  // canonical host CSR (the result of the boundary's index work)
   qp_ctx* ctx;
   int64_t nrows, ncols, nnz;
   qp::HostVec<int64_t> rowptr;
   qp::HostVec<int32_t> col;
   qp::HostVec<cplx> vals;
-};
-
-struct HostLayoutData {
-  int format = QP_FMT_RBCSR;
-  std::vector<int64_t> bptr;   // RBCSR: all entries; HRB: upper section (c >= r)
-  std::vector<int64_t> lptr;   // HRB: lower section (c < r)
-  std::vector<int32_t> nlow;   // HRB: number of lower entries per row
-  std::vector<int64_t> cmeta, lcmeta;  // per block: (byte offset of the column section << 1) | is16
-  int64_t stored = 0, lstored = 0;
 };
 
 struct qp_operator {
@@ -283,6 +251,21 @@ inline int dev_alloc(T** p, size_t count) {
     int rc__ = (expr);           \
     if (rc__ != QP_OK) return rc__; \
   } while (0)
+
+// a new device array holding host_data[0, count)
+template <class T, class U>
+inline int dev_upload(T** p, const U* host_data, size_t count) {
+  static_assert(sizeof(T) == sizeof(U), "same element size on both sides");
+  QP_CHECK(dev_alloc(p, count));
+  if (count > 0) QP_HIP(hipMemcpy(*p, host_data, count * sizeof(T), hipMemcpyHostToDevice));
+  return QP_OK;
+}
+// free a device array (if there is one) and forget it
+template <class T>
+inline void dev_release(T*& p) {
+  if (p) (void)hipFree((void*)p);
+  p = nullptr;
+}
 
 // sum kRedBlocks partials on the host in index order
 inline cplx sum_partials(const double2* h) {

@@ -2,7 +2,7 @@
 // completion of open-boundary grids (lattice_fill), the strip-walk plan of a Hermitian-packed lattice (build_walk_plan: shape
 // parser, run detection, positions), the column-blocked mirror of an operator with irregular columns (build_colblock), the batched path's row walk and LDS tiles
 // (operator_spmm_order, operator_spmm_tiles; moved here in round 6).
-// Split out of engine_core.hip in round 4; called from qp_operator_create / operator_build_device there.
+// Called from qp_operator_create / operator_build_device (engine_operator.hip).
 #include <atomic>
 #include <numeric>
 
@@ -143,9 +143,9 @@ static bool parse_walk_shape(const std::vector<int64_t>& dl, WalkShape& w) { ret
 
 int build_walk_plan(qp_operator* op) {
   qp::WalkPlan& P = op->walk;
-  if (P.edge_map) (void)hipFree(P.edge_map);
+  dev_release(P.edge_map);
   P = qp::WalkPlan();
-  if (op->walk2.edge_map) (void)hipFree(op->walk2.edge_map);
+  dev_release(op->walk2.edge_map);
   op->walk2 = qp::WalkPlan();
   DevMatrix& A = op->A;
   A.walk = nullptr;
@@ -250,8 +250,7 @@ int build_walk_plan(qp_operator* op) {
   P.U0 = U0;
   P.ustride = (int)ustride;
   P.n_edge = (int64_t)edge.size();
-  QP_CHECK(dev_alloc(&P.edge_map, std::max<size_t>(edge.size(), 1)));
-  if (!edge.empty()) QP_HIP(hipMemcpy(P.edge_map, edge.data(), edge.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  QP_CHECK(dev_upload(&P.edge_map, edge.data(), edge.size()));
   P.valid = 1;
   A.walk = &P;
   // the two-term walk's plan: the region in which phase Z (term m + 1 of block t - K) finds y of the K blocks on either side formed
@@ -266,40 +265,10 @@ int build_walk_plan(qp_operator* op) {
     for (int64_t b = 0; b < Q.W0; ++b) edge2.push_back((int32_t)b);
     for (int64_t b = Q.R1; b < nb; ++b) edge2.push_back((int32_t)b);
     Q.n_edge = (int64_t)edge2.size();
-    QP_CHECK(dev_alloc(&Q.edge_map, std::max<size_t>(edge2.size(), 1)));
-    QP_HIP(hipMemcpy(Q.edge_map, edge2.data(), edge2.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    QP_CHECK(dev_upload(&Q.edge_map, edge2.data(), edge2.size()));
     Q.valid = 1;
   }
   return QP_OK;
-}
-
-// position of every union-CSR entry in the operator's value array (-(position) - 1: the complex conjugate of that value --
-// the lower entries of a Hermitian-packed operator)
-void csr_value_map(const qp_operator* op, std::vector<int64_t>& map) {
-  const DevMatrix& A = op->A;
-  const auto& ur = op->u_rowptr;
-  const auto& uc = op->u_col;
-  map.assign((size_t)std::max<int64_t>(A.nnz, 1), 0);
-  parallel_rows(A.nrows, [&](int64_t r_begin, int64_t r_end) {
-    for (int64_t r = r_begin; r < r_end; ++r) {
-      const int64_t nl = (A.format == QP_FMT_HRB) ? op->layout.nlow[r] : 0;
-      for (int64_t k = 0; k < ur[r + 1] - ur[r]; ++k) {
-        int64_t m;
-        if (qp::csr_layout(A.format)) {
-          m = ur[r] + k;
-        } else if (k >= nl) {
-          m = rb_val_pos(op->layout.bptr, r, k - nl);
-        } else {
-          const int64_t c = uc[ur[r] + k];
-          const int32_t* b = uc.data() + ur[c];
-          const int32_t* e = uc.data() + ur[c + 1];
-          const int64_t kk = (std::lower_bound(b, e, (int32_t)r) - b) - op->layout.nlow[c];
-          m = -rb_val_pos(op->layout.bptr, c, kk) - 1;
-        }
-        map[ur[r] + k] = m;
-      }
-    }
-  });
 }
 
 // Column-blocked mirror (device.h: ColBlockPlan; kernels_colblock.hip) for an operator whose gathers are irregular.
@@ -397,7 +366,7 @@ int build_colblock(qp_operator* op) {
     segptr[(size_t)(ntiles * P)] = (int32_t)run;
   }
   std::vector<int64_t> vmap;
-  csr_value_map(op, vmap);
+  csr_value_map(op->layout, A.nrows, ur, uc, vmap);
   std::vector<uint16_t> rowoff((size_t)(ntiles * P) * (size_t)(TR + 1));
   std::vector<uint32_t> cols((size_t)nnz);
   std::vector<int64_t> map((size_t)nnz);
@@ -419,15 +388,11 @@ int build_colblock(qp_operator* op) {
       for (int64_t c = 0; c < P; ++c) rowoff[(size_t)(t * P + c) * (size_t)(TR + 1) + (size_t)TR] = (uint16_t)fill[(size_t)c];
     }
     }, 512);
-  QP_CHECK(dev_alloc(&C.segptr, segptr.size()));
-  QP_CHECK(dev_alloc(&C.rowoff, rowoff.size()));
-  QP_CHECK(dev_alloc(&C.cols, cols.size()));
-  QP_CHECK(dev_alloc(&C.map, map.size()));
+  QP_CHECK(dev_upload(&C.segptr, segptr.data(), segptr.size()));
+  QP_CHECK(dev_upload(&C.rowoff, rowoff.data(), rowoff.size()));
+  QP_CHECK(dev_upload(&C.cols, cols.data(), cols.size()));
+  QP_CHECK(dev_upload(&C.map, map.data(), map.size()));
   QP_CHECK(dev_alloc(&C.vals, (size_t)nnz));
-  QP_HIP(hipMemcpy(C.segptr, segptr.data(), segptr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  QP_HIP(hipMemcpy(C.rowoff, rowoff.data(), rowoff.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  QP_HIP(hipMemcpy(C.cols, cols.data(), cols.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  QP_HIP(hipMemcpy(C.map, map.data(), map.size() * sizeof(int64_t), hipMemcpyHostToDevice));
   C.log2w = log2w;
   C.P = (int)P;
   C.rpt = rpt;
@@ -724,8 +689,7 @@ int operator_spmm_order(qp_operator* op, int batch, const int32_t** order_out) {
     *order_out = op->m_order;
     return QP_OK;
   }
-  if (op->m_order) (void)hipFree(op->m_order);
-  op->m_order = nullptr;
+  dev_release(op->m_order);
   op->m_order_valid = true;
   op->m_order_batch = batch;
   op->m_order_knob = knob;
@@ -735,8 +699,7 @@ int operator_spmm_order(qp_operator* op, int batch, const int32_t** order_out) {
   int64_t g = 0, sw = 0;
   spmm_walk_host(op, batch, knob, &order, &g, &sw);
   if (order.empty()) return QP_OK;
-  QP_CHECK(dev_alloc(&op->m_order, order.size()));
-  QP_HIP(hipMemcpy(op->m_order, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  QP_CHECK(dev_upload(&op->m_order, order.data(), order.size()));
   op->m_order_g = g;
   op->m_order_sw = sw;
   *order_out = op->m_order;
@@ -825,9 +788,9 @@ int operator_spmm_tiles(qp_operator* op, const qp::SpmmTiles** out) {
   const int knob = ctx->tun.spmm_strip;
   *out = nullptr;
   if (!P.built || P.knob != knob) {
-    if (P.tiles) (void)hipFree(P.tiles);
-    if (P.rest) (void)hipFree(P.rest);
-    if (P.tab) (void)hipFree(P.tab);
+    dev_release(P.tiles);
+    dev_release(P.rest);
+    dev_release(P.tab);
     P = qp::SpmmTiles();
     P.built = true;
     P.knob = knob;
@@ -864,13 +827,10 @@ int operator_spmm_tiles(qp_operator* op, const qp::SpmmTiles** out) {
         tab[(size_t)(qp::kSpmmTileSlots + qp::kSpmmTileMaxEntries * 16 + w)] = (int32_t)((int64_t)i * P.g + j);
         tab[(size_t)(qp::kSpmmTileSlots + qp::kSpmmTileMaxEntries * 16 + 16 + w)] = own * 64 * (int32_t)sizeof(double2);
       }
-      QP_CHECK(dev_alloc(&P.tab, tab.size()));
-      QP_HIP(hipMemcpy(P.tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-      QP_CHECK(dev_alloc(&P.tiles, tiles.size()));
-      QP_HIP(hipMemcpy(P.tiles, tiles.data(), tiles.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+      QP_CHECK(dev_upload(&P.tab, tab.data(), tab.size()));
+      QP_CHECK(dev_upload(&P.tiles, tiles.data(), tiles.size()));
       if (!rest.empty()) {
-        QP_CHECK(dev_alloc(&P.rest, rest.size()));
-        QP_HIP(hipMemcpy(P.rest, rest.data(), rest.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        QP_CHECK(dev_upload(&P.rest, rest.data(), rest.size()));
       }
       P.ntiles = (int64_t)tiles.size();
       P.nrest = (int64_t)rest.size();

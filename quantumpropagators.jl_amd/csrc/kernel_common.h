@@ -372,7 +372,7 @@ typedef int i2v __attribute__((ext_vector_type(2)));
 // Column indices of quad q for this lane.  A block stores either int32 columns or, when
 // every column of the block is within +-32767 of its row (banded H), int16 deltas to the
 // lane's own row: 2 instead of 4 bytes per entry of index traffic; a stencil block one distance per
-// slot (mode 2); a block-map block (mode 3: engine_core.hip, encode_col_sections) one column block per
+// slot (mode 2); a block-map block (mode 3: operator_layout.cpp, encode_col_sections) one column block per
 // slot + one byte per entry.
 template <bool NT>
 __device__ __forceinline__ int4 ld_cols(const char* __restrict__ colbytes, int64_t meta, int q, int lane, int rowc) {
@@ -401,7 +401,7 @@ __device__ __forceinline__ int4 ld_cols(const char* __restrict__ colbytes, int64
   return ld_col<NT>(reinterpret_cast<const int4*>(p) + (size_t)q * 64 + lane);
 }
 
-// one slot of a stencil lower section (engine_core.hip: LowerStencilSlot): column = row + delta,
+// one slot of a stencil lower section (operator_layout.h: LowerStencilSlot): column = row + delta,
 // the conj-transposed value sits at pb(column block) + column % 64
 struct LowerStencilSlot {
   int delta, cb0;

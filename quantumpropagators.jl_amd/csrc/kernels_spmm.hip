@@ -93,7 +93,7 @@ __global__ __launch_bounds__(kThreads) void csr_spmm_kernel(const int64_t* __res
 // i with H[i, r] != 0.  For H = H_a (x) 1 + 1 (x) H_c -- the lattice / tensor-product operators of
 // BASELINE's workloads: offsets +-1..4 and +-1024 k -- those rows are a span of 8192 rows apart in
 // natural order, 8 MiB of X at 64 states, twice an XCD's L2.  `order` (operator_spmm_order in
-// engine_core.hip) lists the rows strip by strip -- for a strip of `sw` inner indices c, all outer
+// engine_plans.hip) lists the rows strip by strip -- for a strip of `sw` inner indices c, all outer
 // indices a in turn, i = a g + c -- so that the +-k g neighbours are the rows visited just before and
 // just after, and the window a wave can hit in L2 shrinks to (2 a_max + 1) sw rows.  Any
 // permutation gives the same values bit for bit (rows are independent); it only moves traffic.
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(64 * WS) void spmm_rows_smem_kernel(const int64_t* 
 }
 
 // ---------------------------------------------------------------------------
-// LDS-staged 4 x 4 tiles of a lattice operator's interior rows (SpmmTiles, device.h; plan: operator_spmm_tiles in engine_core.hip).
+// LDS-staged 4 x 4 tiles of a lattice operator's interior rows (SpmmTiles, device.h; plan: operator_spmm_tiles in engine_plans.hip).
 // Sixteen wavefronts = the sixteen rows r0 + i g + j of the tile, lane = state.  The workgroup first loads the 16 + 8 K + 8 NN
 // distinct panel rows its rows read -- slots [(4 + 2 K) strip steps][4 columns], then [4 strip steps][2 NN near-halo columns] --
 // five per wavefront, issued before the row-local streams so that the barrier waits on them as little as possible; after the

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE ONLY (tests/test_cabi_host.py::test_host_index_work_under_sanitizers): a host stand-in for the handful of
-// HIP runtime calls that the library's HOST index work makes (csrc/engine_core.hip, engine_plans.hip: format choice, lattice
+// HIP runtime calls that the library's HOST index work makes (csrc/engine_core.hip, engine_operator.hip, engine_plans.hip: format choice, lattice
 // completion, strip-walk plan, column encodings, column-blocked mirror, value dictionary, the get_csr round trip), so that
 // exactly those sources compile with g++ -fsanitize=address,undefined on a box without a GPU.  "Device" memory is heap memory:
 // AddressSanitizer then checks every copy into and out of a device array against the size it was allocated with -- the
@@ -39,7 +39,11 @@ static inline hipError_t hipSetDevice(int) { return hipSuccess; }
 static inline hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 static inline hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 static inline hipError_t hipDeviceGetAttribute(int* v, hipDeviceAttribute_t, int) { *v = 256; return hipSuccess; }
+#ifdef QP_SHIM_ZERO_ALLOC   // (the harness's --digest mode: bytes nobody writes hash the same in every build)
+static inline hipError_t hipMalloc(void** p, size_t n) { *p = std::calloc(n ? n : 1, 1); return *p ? hipSuccess : 2; }
+#else
 static inline hipError_t hipMalloc(void** p, size_t n) { *p = std::malloc(n ? n : 1); return *p ? hipSuccess : 2; }
+#endif
 template <class T> static inline hipError_t hipMalloc(T** p, size_t n) { return hipMalloc(reinterpret_cast<void**>(p), n); }
 static inline hipError_t hipFree(void* p) { std::free(p); return hipSuccess; }
 static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { return hipMalloc(p, n); }

@@ -2,17 +2,23 @@
 // host before a kernel ever runs -- union pattern, Hermitian check, format choice, lattice completion, strip-walk plan, column
 // encodings (int32 / int16 / stencil / block map), Hermitian packing with transposed positions, column-blocked mirror, value
 // dictionary -- and the decoders of qp_operator_get_csr, compiled from the library's own sources (csrc/engine_core.hip,
-// csrc/engine_plans.hip, csrc/host_numerics.cpp) with g++ against tests/hip_host_shim (device memory = heap memory, so the
+// csrc/engine_operator.hip, csrc/engine_plans.hip here; csrc/operator_layout.cpp and csrc/host_numerics.cpp beside it as
+// ordinary C++) with g++ against tests/hip_host_shim (device memory = heap memory, so the
 // sanitizer checks every copy into a "device" array against its allocation) and driven by a fuzz over the shapes that have bitten:
 // tall (5681 x 358: the round-4 GPU memory fault), wide, 1 row, fewer than 64 rows, empty rows, lattices, grids, spin chains.
 // Checked per case: the get_csr round trip reproduces the input exactly; EVERY stored slot of every row block -- real entries,
 // pads, the lanes beyond the last row -- decodes to a column inside the matrix; every pad carries the value zero in every term;
 // every transposed position of a Hermitian-packed operator is -1 (pad) or inside the value array.
 // Built and run by tests/test_cabi_host.py::test_host_index_work_under_sanitizers (CPU only).
+// `--digest`: per case one line with the format, the scalar fields of the layout structs and a 64-bit FNV-1a hash over the
+// declared extent of every "device" array the operator owns -- two builds of the library lay operators out bit-identically iff
+// their outputs agree.  For this mode build WITHOUT the sanitizers and with -DQP_SHIM_ZERO_ALLOC (bytes the build never writes
+// then compare equal).  The values depend on the standard library's distributions: compare, do not store.
 #include <cstdio>
 #include <random>
 
 #include "../quantumpropagators.jl_amd/csrc/engine_core.hip"
+#include "../quantumpropagators.jl_amd/csrc/engine_operator.hip"
 #include "../quantumpropagators.jl_amd/csrc/engine_plans.hip"
 
 // ---- host stand-ins of the few launches the creation path makes (values only; no kernel runs in this build) ---------------
@@ -117,6 +123,67 @@ int64_t decode_any(const char* bytes, int64_t meta, int64_t k, int l, int64_t ro
 }
 
 int64_t n_cases = 0, n_walked = 0, n_hrb = 0, n_coded = 0, n_cb = 0, n_dense = 0;
+bool g_digest = false;
+
+// --digest: see the head of this file
+void print_digest(const qp_operator* op, const char* what) {
+  uint64_t h = 1469598103934665603ull;
+  auto bytes = [&](const void* p, size_t n) {
+    for (size_t i = 0; i < n; ++i) h = (h ^ static_cast<const unsigned char*>(p)[i]) * 1099511628211ull;
+  };
+  std::string scalars;
+  auto num = [&](long long v) { scalars += " " + std::to_string(v); };
+  const DevMatrix& A = op->A;
+  const size_t nb = (size_t)A.nblocks;
+  for (long long v : {(long long)A.nrows, (long long)A.ncols, (long long)A.nnz, (long long)A.stored, (long long)A.nblocks, (long long)A.colbytes,
+                      (long long)A.lanes_per_row, (long long)A.lcolbytes, (long long)A.lstored, (long long)op->planes.size(), (long long)op->sparse_from,
+                      (long long)op->n_support, (long long)op->planes_real, (long long)op->n_lattice_fill, (long long)op->cv_reason})
+    num(v);
+  if (qp::csr_layout(A.format)) {
+    bytes(A.rowptr, ((size_t)A.nrows + 1) * 8);
+    bytes(A.cols, (size_t)A.nnz * 4);
+  } else {
+    bytes(A.bptr, (nb + 1) * 8);
+    bytes(A.cmeta, nb * 8);
+    bytes(A.cols, (size_t)A.colbytes);
+  }
+  if (A.format == QP_FMT_HRB) {
+    bytes(A.lptr, (nb + 1) * 8);
+    bytes(A.lcmeta, nb * 8);
+    bytes(A.lcols, (size_t)A.lcolbytes);
+    bytes(A.lpos, (size_t)A.lstored * 4);
+  }
+  for (const double2* p : op->planes) bytes(p, (size_t)A.stored * 16);
+  if (op->sparse_from >= 0) {
+    bytes(op->support, (size_t)op->n_support * 4);
+    bytes(op->support_vals, (size_t)(op->nops - op->sparse_from) * (size_t)op->n_support * 16);
+  }
+  for (const qp::WalkPlan* P : {&op->walk, &op->walk2}) {
+    for (long long v : {(long long)P->valid, (long long)P->nn, (long long)P->K, (long long)P->z0, (long long)P->S, (long long)P->xl, (long long)P->glong,
+                        (long long)P->glong1, (long long)P->fd, (long long)P->g, (long long)P->R0, (long long)P->R1, (long long)P->W0, (long long)P->U0,
+                        (long long)P->ustride, (long long)P->n_edge})
+      num(v);
+    for (int v : P->near) num(v);
+    if (P->valid) bytes(P->edge_map, (size_t)P->n_edge * 4);
+  }
+  const qp::ColBlockPlan& B = op->cb;
+  for (long long v : {(long long)B.valid, (long long)B.log2w, (long long)B.P, (long long)B.rpt, (long long)B.max_seg, (long long)B.ntiles, (long long)B.nnz, (long long)B.use_real}) num(v);
+  if (B.valid) {
+    bytes(B.segptr, (size_t)(B.ntiles * B.P + 1) * 4);
+    bytes(B.rowoff, (size_t)(B.ntiles * B.P) * (size_t)(64 * B.rpt + 1) * 2);
+    bytes(B.cols, (size_t)B.nnz * 4);
+    bytes(B.map, (size_t)B.nnz * 8);
+    bytes(B.vals, (size_t)B.nnz * 16);
+  }
+  const qp::CodedVals& C = op->cv;
+  for (long long v : {(long long)C.valid, (long long)C.ntab, (long long)C.ntables, (long long)C.use_real}) num(v);
+  if (C.valid) {
+    bytes(C.codes, (size_t)A.stored);
+    bytes(C.tptr, nb * 8);
+    for (const double2* p : op->cv_tplanes) bytes(p, (size_t)C.ntab * 16);
+  }
+  std::printf("digest %s | format %d |%s | %016llx\n", what, A.format, scalars.c_str(), (unsigned long long)h);
+}
 
 void check_operator(qp_ctx* ctx, const std::vector<Csr>& terms, int ncoeffs, int format, const char* what) {
   std::vector<qp_matrix*> ms;
@@ -141,6 +208,7 @@ void check_operator(qp_ctx* ctx, const std::vector<Csr>& terms, int ncoeffs, int
   if (op->walk.valid) ++n_walked;
   if (op->cv.valid) ++n_coded;
   if (op->cb.valid) ++n_cb;
+  if (g_digest) print_digest(op, what);
   // ---- round trip: one term, unit coefficient -> the input bit for bit (more terms: the union pattern, values summed)
   {
     const int64_t nnz = A.nnz;
@@ -357,7 +425,8 @@ Csr tfim(int n) {
 
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+  g_digest = argc > 1 && std::strcmp(argv[1], "--digest") == 0;
   qp_ctx* ctx = nullptr;
   if (qp_ctx_create(0, nullptr, &ctx) != QP_OK) {
     std::fprintf(stderr, "qp_ctx_create: %s\n", qp::g_last_error.c_str());
@@ -392,6 +461,7 @@ int main() {
       REQUIRE(qp_matrix_create(ctx, 3, 3, 9, t.rp.data(), idx.data(), t.val.data(), QP_VAL_C128, QP_LAYOUT_CSR, 0, QP_FMT_AUTO, &m) == QP_OK, "dup: matrix");
       qp_operator* op = nullptr;
       REQUIRE(qp_operator_create(ctx, &m, 1, 0, fmt, &op) == QP_OK, "dup: operator (format %d): %s", fmt, qp::g_last_error.c_str());
+      if (g_digest) print_digest(op, "dup");
       const int64_t nnz = op->A.nnz;
       std::vector<int64_t> rp(4);
       std::vector<int32_t> col((size_t)nnz);

@@ -446,20 +446,24 @@ def test_host_numerics_under_sanitizers(tmp_path):
 def test_host_index_work_under_sanitizers(tmp_path):
     """the HOST INDEX WORK of operator creation -- format choice, lattice completion, strip-walk plan, column
     encodings, Hermitian packing, column-blocked mirror, value dictionary, the get_csr decoders -- compiled from the library's own
-    sources (csrc/engine_core.hip, engine_plans.hip, host_numerics.cpp) with g++ -fsanitize=address,undefined against a host
+    sources (csrc/engine_core.hip, engine_operator.hip, engine_plans.hip, operator_layout.cpp, host_numerics.cpp) with g++ -fsanitize=address,undefined against a host
     stand-in of the HIP runtime (tests/hip_host_shim: device memory = heap memory, so every copy into a "device" array is
     bounds-checked) and fuzzed over tall / wide / 1-row / N < 64 / empty-row shapes, lattices and spin chains
     (tests/sanitize_host_index.cpp; the 5681 x 358 operator of the round-4 GPU memory fault is the first case).  Every stored slot
-    -- pads and the lanes beyond the last row included -- must decode to a column inside the matrix, every pad must be zero."""
+    -- pads and the lanes beyond the last row included -- must decode to a column inside the matrix, every pad must be zero.
+    The layout unit (csrc/operator_layout.cpp) must stay pure host code: it compiles without the HIP stand-in on the include path."""
     import shutil
     import subprocess
     if shutil.which("g++") is None:
         pytest.skip("g++ not available")
     csrc = os.path.join(ROOT, "quantumpropagators.jl_amd", "csrc")
     exe = str(tmp_path / "host_index_san")
+    pure = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", csrc, os.path.join(csrc, "operator_layout.cpp")], capture_output=True, text=True)
+    assert pure.returncode == 0, pure.stderr[-3000:]
     build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-x", "c++",
                             "-I", os.path.join(ROOT, "tests", "hip_host_shim"), "-I", csrc,
                             os.path.join(ROOT, "tests", "sanitize_host_index.cpp"), os.path.join(csrc, "host_numerics.cpp"),
+                            os.path.join(csrc, "operator_layout.cpp"),
                             "-o", exe, "-lpthread"], capture_output=True, text=True)
     if build.returncode != 0 and "sanitize" in build.stderr and "cannot find" in build.stderr:
         pytest.skip("sanitizer runtime not installed")

@@ -69,7 +69,7 @@ def test_device_format_roundtrip_bit_exact(ctx, fmt, n):
 @pytest.mark.parametrize("fmt", [L.FMT_HRB, L.FMT_RBCSR, L.FMT_CSR])
 def test_large_value_plane_roundtrip_bit_exact(ctx, fmt):
     """A value plane of more than 256 MiB goes to the device in 64-MiB chunks through two pinned buffers while the host threads lay
-    out the next chunk (engine_core.hip: operator_build_device_impl), and `qp_matrix_create` copies and checks its arrays on the
+    out the next chunk (engine_operator.hip: upload_plane_staged), and `qp_matrix_create` copies and checks its arrays on the
     host threads: the read-back of every device format reproduces the input bit for bit (N = 2^21 + 77 rows, 16 entries per row --
     a ragged last row block and a last chunk that is not full)."""
     N = (1 << 21) + 77

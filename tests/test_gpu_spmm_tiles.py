@@ -1,4 +1,4 @@
-"""GPU tests of the LDS-staged tiles of the batched Chebyshev term (csrc/kernels_spmm.hip: spmm_tile_kernel; plan: engine_core.hip
+"""GPU tests of the LDS-staged tiles of the batched Chebyshev term (csrc/kernels_spmm.hip: spmm_tile_kernel; plan: engine_plans.hip
 operator_spmm_tiles; BASELINE configs[4]): a lattice operator's interior rows are summed by workgroups that stage the 4 x 4 patch's
 operands once -- the same entries in the same order as the row kernel, so the same bits; the reference would run `batch` independent
 `cheby!` calls (src/cheby.jl:151-214), which is what the oracle does."""

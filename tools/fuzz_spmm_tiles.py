@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fuzz the LDS-staged tiles of the batched Chebyshev term (csrc/kernels_spmm.hip: spmm_tile_kernel; plan: engine_core.hip
+"""Fuzz the LDS-staged tiles of the batched Chebyshev term (csrc/kernels_spmm.hip: spmm_tile_kernel; plan: engine_plans.hip
 operator_spmm_tiles) against the row kernel (bit for bit) and the NumPy oracle (1e-10): random lattice operators -- near distances a
 random subset of 1..4 (or none), far distances random multiples m g, |m| <= 4 (gaps allowed), g any value from 64 to 700 (multiples of 4
 or not), with or without diagonal, periodic wrap-around (synth.hermitian_offsets_csr) or open ends (the wrapped entries removed: rows
