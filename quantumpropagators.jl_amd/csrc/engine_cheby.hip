@@ -327,9 +327,13 @@ int qp_cheby_step(qp_cheby* w, qp_operator* op, qp_state* psi, const double* a, 
     QP_CHECK(dev_alloc(&w->bufC, (size_t)w->n));
     QP_CHECK(dev_alloc(&w->bufD, (size_t)w->n));
   }
-  // launch-bound systems (a term takes less than its launch): replay the step as a hipGraph
+  // launch-bound systems (a term takes less than its launch): replay the step as a hipGraph.  Never for a matrix-free operator:
+  // the key below knows an operator by its stored arrays (all NULL there), and the owner's launch picks its kernel on the host from
+  // the CURRENT coefficients (engine_pauli.hip: real-only paths, diagonal vector real or complex) -- a captured step would replay
+  // another operator's, or an earlier coefficient set's, launches
   bool done = false;
-  if (ctx->tun.cheby_graph && !check_normalization && ctx->stream != nullptr && ctx->stream != hipStreamLegacy) {
+  if (ctx->tun.cheby_graph && !check_normalization && A.format != QP_FMT_MATFREE && ctx->stream != nullptr &&
+      ctx->stream != hipStreamLegacy) {
     qp_cheby::GraphKey key;
     key.vals = A.vals_r ? (const void*)A.vals_r : (const void*)A.vals;
     key.cols = A.cols;
