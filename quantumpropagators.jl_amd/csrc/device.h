@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "layout_constants.h"
+#include "walk_geometry.h"
 
 namespace qp {
 
@@ -68,37 +69,6 @@ struct DevMatrix {
   double2* (*matfree_scratch)(void* self) = nullptr;   // n entries of workspace for the Chebyshev term
   // optional: the fused Chebyshev term of the owner's own kernel (engine_pauli.hip); without it the term is apply + epilogue
   int (*matfree_cheby)(hipStream_t s, void* self, const double2* x, const struct ChebyEpi& e, Stats* st) = nullptr;
-};
-
-// ---- strip walk over a lattice operator (Hermitian-packed format) -----------------------------------------------
-// A run of row blocks [R0, R1) that all carry the same stencil: upper section
-//   [z0 slots at distance 0 (the diagonal)] [nn near distances 0 < d_1 < ... < d_nn <= 16] [K far distances m g, m = 1..K]
-//   [pads], lower section its mirror image [-K g ... -g] [-d_nn ... -d_1]; S = ceil(g / 64) column chunks per strip step.  Inside the run the position of
-// every value is a formula (U0 + (b - R0) ustride + 64 slot + lane), and a wavefront that WALKS down one strip column --
-// row blocks b, b + S, b + 2 S, ... -- finds everything a block needs beyond its own streams in what it loaded for the
-// blocks before: the gathered elements x[r + m g] are the row-local elements of the blocks m steps ahead / behind (a ring
-// of 2 K + 1 registers, one new load per step), the conj-transposed values of the far lower entries are the far upper
-// values it streamed m steps ago (a FIFO in LDS), the near gathers and the near conj-transposed values are lane shifts
-// of the block's own element / values, staged through a per-wavefront LDS window with a halo of the neighbouring block.
-// Blocks outside [W0, R1) (W0 = R0 + K S: the first blocks whose history lies inside the run; the periodic wrap-around,
-// a ragged end) are listed in edge_map and take the per-block code path in the same launch.
-constexpr int kWalkMaxNear = 8;
-constexpr int kWalkHalo = 16;      // largest near distance
-struct WalkPlan {
-  int valid = 0;
-  int nn = 0, K = 0, z0 = 0;  // shape of the stencil (see above)
-  int S = 0;                  // 64-row column chunks per strip step: ceil(g / 64)
-  int xl = 0;                 // 1: one more pair of distances +- glong beyond the ring's reach (loaded directly); 2: two, +- glong1 and +- glong
-  int64_t glong = 0;          // the longest distance of the stencil
-  int64_t glong1 = 0;         // xl = 2: the shorter long distance, K g < glong1 < glong
-  int fd = 0;                 // 1: diagonal far neighbours -- the far distances of strip step m are m g - 1, m g, m g + 1 (three slots per step)
-  int64_t g = 0;              // rows per strip step (the far distances are g, 2 g, .., K g); need not be a multiple of 64
-  int near[kWalkMaxNear] = {0};
-  int64_t R0 = 0, R1 = 0, W0 = 0;
-  int64_t U0 = 0;             // bptr[R0]
-  int ustride = 0;            // stored upper values per row block (64 x padded width)
-  int32_t* edge_map = nullptr;   // device: the blocks outside [W0, R1)
-  int64_t n_edge = 0;
 };
 
 // ---- column-blocked mirror (kernels_colblock.hip) ----------------------------------------------------------------------
@@ -241,21 +211,7 @@ int launch_arnoldi_onepass_sweep(hipStream_t s, const DevMatrix& A, const double
                                  double* svals, double* nu_dev, double dt, double2* hess_map, double* norms_map, double* nu_map,
                                  unsigned* flags_map, unsigned flag_value, Stats* st);
 // the strip walk for the fused Chebyshev term of a whole Hermitian-packed lattice operator; *launched = false when the
-// plan's shape has no kernel instance (the caller then takes the per-block kernel)
-// is there a strip-walk kernel instance for this stencil shape?  (The dispatch of kernels_walk_impl.h: launch_shape instantiates
-// exactly these; inline here so that the host planners -- and their sanitizer build, tests/sanitize_host_index.cpp -- see the same list.)
-// near distances 1..4 of at most 16 rows, far reach 1..4 strip steps, with or without a diagonal
-// ... and, with one or two long pairs beyond the ring (xl = 1, 2), near 1..2 and one or two far distances
-// ... and, with diagonal far neighbours (fd = 1: m g - 1, m g, m g + 1), near 1..2, one strip step and at most one long pair
-inline bool walk_shape_supported(int nn, int K, int z0, int xl = 0, int fd = 0) {
-  if (fd) return fd == 1 && (xl == 0 || xl == 1) && K == 1 && nn >= 1 && nn <= 2 && (z0 == 0 || z0 == 1);
-  if (xl) return (xl == 1 || xl == 2) && nn >= 1 && nn <= 2 && (K == 1 || K == 2) && (z0 == 0 || z0 == 1);
-  return nn >= 1 && nn <= 4 && K >= 1 && K <= 4 && (z0 == 0 || z0 == 1);
-}
-// the two-term strip walk (kernels_walk2.hip): both terms of a pair (m, m + 1) on the two-term region of plan `P2`, term m of its edge list
-inline bool walk2_shape_supported(int nn, int K, int z0) {
-  return (z0 == 0 || z0 == 1) && nn >= 1 && nn <= 4 && K >= 1 && K <= 4;
-}
+// plan's shape has no kernel instance (the caller then takes the per-block kernel); how a launch is cut: walk_geometry.h
 int launch_hrb_walk2_cheby(hipStream_t s, const DevMatrix& A, const WalkPlan& P2, const double2* x, const ChebyEpi& e1,
                            const ChebyEpi& e2, const Tuning& tun, bool* launched);
 int launch_hrb_walk_cheby(hipStream_t s, const DevMatrix& A, const double2* x, const ChebyEpi& e, const Tuning& tun,
@@ -286,13 +242,10 @@ inline int dense_gemv_grid(int64_t nrows) {
 // qp_ctx_tuning_set); qp_tuning_set only changes the defaults that contexts created afterwards start
 // from, so handles driven from different threads never observe each other's switches.
 // fixed choices that were knobs while they were being measured (docs/history/): the density from which AUTO lays an operator out dense,
-// the resident wavefronts per CU the column-blocked mirror is sized for (24 and 32 measured slower), the compute units an interior strip
-// walk leaves to the boundary launch and the collective's kernel
+// the resident wavefronts per CU the column-blocked mirror is sized for (24 and 32 measured slower)
 constexpr int kDenseMinDensityPct = 75;
 constexpr int kCbWavesPerCu = 16;
 constexpr int kCbMinLog2N = 20;     // column-blocked mirror: smallest number of columns (log2) it is built for (measured: 2^18 columns 0.9 x, 2^19 1.04 x, 2^20 1.37 x, 2^21 1.62 x, 2^22 1.52 x)
-constexpr int kWalkReserveCu = 8;
-constexpr int kWalkEdgeSteps = 4;   // strip walk: a wavefront that also takes an edge block walks this many steps less (a block on the per-block path is three dependent rounds of loads; a step of the walk takes about one)
 
 struct Tuning {
   int rbcsr_variant = 15;     // bit 0 nt matrix loads, bit 1 early row-local loads, bit 2 deeper unroll, bit 3 (Hermitian-packed kernel) all loads of an all-stencil block up front (A/B in profiles/)
@@ -331,6 +284,9 @@ struct Tuning {
   int walk_min_blocks = 3072; // strip walk: smallest number of walkable row blocks for which the plan is used
   int spmm_nt = 1;            // nontemporal matrix / row-local streams in the batched SpMM kernel: 0 never, 2 always, 1 for large panels
 };
+// what the cut of a strip walk (walk_geometry.h) reads of an operator and of the knobs
+inline WalkMatrix walk_matrix(const DevMatrix& A) { return WalkMatrix{A.nblocks, A.nrows, A.ncols, A.vals_r != nullptr}; }
+inline WalkKnobs walk_knobs(const Tuning& t) { return WalkKnobs{t.walk_waves, t.walk_nt, t.walk_dbg, t.walk_min_blocks, t.walk_pair}; }
 // compute units of the CURRENT device (hipGetDevice; asked once per device and cached; 256 if the runtime will not say)
 int device_cu_count();
 // address of the knob called `key` inside `t`, or nullptr

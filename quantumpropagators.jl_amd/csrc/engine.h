@@ -295,3 +295,29 @@ int operator_spmm_tiles(qp_operator* op, const qp::SpmmTiles** out);
 // which terms of a cheby! touch the Psi accumulator (include/qprop.h, qp_acc_defer)
 void acc_schedule(const double* a, int n_coeffs, bool defer, qp_acc_defer* out);
 void set_defer(qp::ChebyEpi& e, const qp_acc_defer* d);
+// ---- set-up of a cheby! shared by the single-state, the batched and the row-partitioned step (engine_cheby.hip) ----------
+// @assert abs(dt) ~ abs(wrk.dt)   (isapprox, rtol = sqrt(eps))   src/cheby.jl:157
+bool cheby_dt_matches(double dt, double wrk_dt);
+struct ChebyScalars {   // src/cheby.jl:156, :158-162, :211
+  double beta;
+  cplx c, phase;
+  ChebyScalars(double Delta, double E_min, double dt);
+};
+// which terms touch Psi's accumulator (acc_schedule) and what the next one finds there
+struct ChebyAcc {
+  std::vector<qp_acc_defer> sched;
+  double a0;
+  bool updated = false;   // has any term written the accumulator yet?
+  ChebyAcc(const double* a, int n_coeffs, bool defer) : sched((size_t)n_coeffs - 1), a0(a[0]) { acc_schedule(a, n_coeffs, defer, sched.data()); }
+  struct Term {
+    const qp_acc_defer* defer;
+    double a_prev;   // the coefficient of v_0 while the accumulator has not been written
+    bool acc_in;     // the term reads the accumulator
+  };
+  Term term(int m) {   // term m is issued next
+    const qp_acc_defer& d = sched[(size_t)m - 1];
+    const Term t{&d, updated ? 0.0 : a0, updated && !d.skip};
+    updated = updated || !d.skip;
+    return t;
+  }
+};

@@ -43,6 +43,151 @@ void set_defer(qp::ChebyEpi& e, const qp_acc_defer* d) {
   e.a_d2 = d->a_d2;
 }
 
+bool cheby_dt_matches(double dt, double wrk_dt) {
+  const double x = std::fabs(dt), y = std::fabs(wrk_dt);
+  return std::fabs(x - y) <= 1.4901161193847656e-08 * std::max(x, y);
+}
+
+ChebyScalars::ChebyScalars(double Delta, double E_min, double dt)
+    : beta((Delta / 2) + E_min),
+      c((dt > 0) ? cplx(0, -2.0) / Delta : cplx(0, 2.0) / Delta),
+      phase(std::exp(cplx(0, -1) * beta * dt)) {}
+
+// the epilogue of one fused term from its operands and scalars; a term that skips the accumulator (defer->skip) carries none
+static qp::ChebyEpi cheby_epi(const double2* xloc, const double2* v0, double2* vout, const double2* acc_in, double2* acc_out,
+                              double2 c, double beta, double a_prev, double a, double2 phase, int apply_phase,
+                              const qp_acc_defer* defer) {
+  const bool skip = defer && defer->skip;
+  qp::ChebyEpi e;
+  e.xloc = xloc;
+  e.v0 = v0;
+  e.vout = vout;
+  e.acc_in = skip ? nullptr : acc_in;
+  e.acc_out = skip ? nullptr : acc_out;
+  e.c = c;
+  e.beta = beta;
+  e.a_prev = a_prev;
+  e.a = a;
+  e.phase = phase;
+  e.apply_phase = apply_phase;
+  e.check_partials = nullptr;
+  set_defer(e, defer);
+  return e;
+}
+
+// the term arguments of the C ABI (qp_cheby_term, qp_cheby_term_split; `who`: the entry point's name): checked, then as an epilogue
+static int cheby_term_args(const char* who, const qp_operator* op, const qp_state* x, int64_t xoff, const qp_state* v0,
+                           qp_state* vout, const qp_state* acc_in, qp_state* acc_out, qp_c128 c, double beta, double a_prev,
+                           double a, qp_c128 phase, const qp_acc_defer* defer, qp::ChebyEpi* e) {
+  if (defer && !defer->skip && (defer->n_defer < 0 || defer->n_defer > 2 || (defer->n_defer > 0 && !v0 && (defer->n_defer == 2 || !acc_in))))
+    return qp::fail(QP_E_BAD_ARG, "%s: deferred accumulation needs v0", who);
+  const int64_t nr = op->A.nrows;
+  if (x->n != op->A.ncols || xoff < 0 || xoff + nr > x->n) return qp::fail(QP_E_BAD_ARG, "%s: x shape / offset mismatch", who);
+  if ((v0 && v0->n != nr) || (vout && vout->n != nr) || (acc_in && acc_in->n != nr) || (acc_out && acc_out->n != nr))
+    return qp::fail(QP_E_BAD_ARG, "%s: local vector length mismatch", who);
+  *e = cheby_epi(x->d + xoff, v0 ? v0->d : nullptr, vout ? vout->d : nullptr, acc_in ? acc_in->d : nullptr,
+                 acc_out ? acc_out->d : nullptr, d2(c), beta, a_prev, a, d2(phase), !(phase.re == 1.0 && phase.im == 0.0), defer);
+  return QP_OK;
+}
+
+// Does a whole-operator cheby! of `op` take the two-term strip walk (kernels_walk2.hip) under the context's knobs?  The rule:
+// walk_geometry.cpp, for an operator whose whole-operator term is the one-term walk of its own plan.
+static bool walk2_wanted(const qp_operator* op) {
+  const qp::Tuning& tun = op->ctx->tun;
+  return tun.hrb_walk && (tun.rbcsr_variant & 31) == 15 && op->A.walk == &op->walk &&
+         qp::walk2_wanted(op->walk, op->walk2, qp::walk_matrix(op->A), qp::walk_knobs(tun), qp::device_cu_count());
+}
+
+// the launches of one cheby! call (src/cheby.jl:171-211): n_coeffs - 1 fused mat-vec + term
+// kernels and, when the result does not land in Psi's buffer, one copy.
+// Term vectors: `cur` holds v_{m-1} (gathered by term m), `prev` holds v_{m-2}.  A one-term launch writes v_m over v_{m-2} in
+// place; a two-term launch (terms m and m + 1 in one pass over the matrix values, kernels_walk2.hip) writes v_m and v_{m+1} to two
+// vectors nobody reads meanwhile -- the neighbouring strip columns still gather from `cur` and `prev` -- so a step that takes pairs
+// rotates four vectors (Psi's, bufA, bufC, bufD) instead of two.
+// `launch_term(x, e)` issues one term: the single-state step's mat-vec kernel, or the panel kernels of the batched step (`panel`:
+// element = (row, state); never in pairs, no check_normalization).
+template <class LaunchTerm>
+static int cheby_step_launches(qp_cheby* w, qp_operator* op, qp_state* psi, const double* a, int n_coeffs, ChebyScalars sc,
+                               bool check_normalization, bool panel, LaunchTerm&& launch_term) {
+  qp_ctx* ctx = op->ctx;
+  const DevMatrix& A = op->A;
+  const int nterms = n_coeffs - 1;
+  double2* P = psi->d;
+  double2* B = w->bufA;
+  double2* ACC = w->acc;
+  double2* result = nullptr;
+  ChebyAcc acc(a, n_coeffs, ctx->tun.acc_defer != 0);
+  bool pairs = !panel && !check_normalization && nterms >= 3 && w->bufC && w->bufD && walk2_wanted(op);   // (qp_cheby_step allocated the two vectors)
+  double2 *cur = P, *prev = nullptr;
+  double2* spare[2] = {w->bufC, w->bufD};      // the two vectors no term of the step is reading
+  // the epilogue of term m, issued next: gathers x, v_{m-2} = v0 -> vout, Psi's accumulator -> acc_out unless the schedule skips it
+  auto epi = [&](int m, const double2* x, const double2* v0, double2* vout, double2* acc_out) {
+    const ChebyAcc::Term t = acc.term(m);
+    return cheby_epi(x, v0, vout, t.acc_in ? ACC : nullptr, acc_out, d2(sc.c), sc.beta, t.a_prev, a[m], d2(sc.phase),
+                     (m == nterms) ? 1 : 0, t.defer);
+  };
+  for (int m = 1; m <= nterms; ++m) {
+    const bool last = (m == nterms);
+    if (m > 1 && pairs && m + 1 <= nterms && !(acc.sched[m - 1].skip == 0 && acc.sched[m].skip == 0)) {
+      // terms m and m + 1 in one pass over the values: y = v_m -> spare[0], z = v_{m+1} -> spare[1]
+      const bool last2 = (m + 1 == nterms);
+      const bool updated_before = acc.updated;
+      const qp::ChebyEpi e1 = epi(m, cur, prev, spare[0], ACC);
+      const qp::ChebyEpi e2 = epi(m + 1, spare[0], cur, last2 ? nullptr : spare[1], ACC);
+      bool launched = false;
+      {
+        const qp::ScopedRange mv_range(ctx->tun.roctx != 0 || qp::ranges_enabled_by_env(), "matrix-vector product");
+        QP_CHECK(qp::launch_hrb_walk2_cheby(ctx->stream, A, op->walk2, cur, e1, e2, ctx->tun, &launched));
+        if (launched) {
+          // term m + 1 of the blocks outside the two-term region: they read y of their neighbours, which the launch above wrote
+          qp::RowSet rs;
+          rs.block_map = op->walk2.edge_map;
+          rs.nmap = op->walk2.n_edge;
+          rs.count = false;
+          QP_CHECK(qp::launch_spmv_cheby(ctx->stream, A, spare[0], e2, &ctx->stats, &rs));
+          ctx->stats.n_launch++;
+          ctx->stats.n_matvec += 2;
+          ctx->stats.spmv_bytes += 2.0 * (20.0 * (double)A.nnz + 4.0 * (double)(A.nrows + 1) + 80.0 * (double)A.nrows);
+        }
+      }
+      if (launched) {
+        result = ACC;
+        double2* const y = spare[0];
+        double2* const z = spare[1];
+        spare[0] = cur;
+        spare[1] = prev;
+        prev = y;
+        cur = z;
+        ++m;
+        continue;
+      }
+      // not taken after all (the kernel's LDS opt-in was refused): this and every later term as one-term launches
+      acc.updated = updated_before;
+      pairs = false;
+    }
+    // m = 1: v0 = Psi; Psi = a1 v0; v1 = c (H v0 - beta v0); Psi += a2 v1     :171-182
+    // m > 1: v2 = c (H v1 - beta v1) + v0 (`prev` holds v0, overwritten in place by v2); Psi += a_i v2; rotate            :186-207
+    double2* const acc_out = (m > 1 && last && cur != P && !pairs) ? P : ACC;  // P may be written only while it is not gathered
+    result = acc_out;
+    qp::ChebyEpi e = epi(m, cur, prev, last ? nullptr : (m == 1 ? B : prev), acc_out);
+    // the reference checks terms i >= 3 only (inside the loop at :186)
+    e.check_partials = (check_normalization && m >= 2) ? w->chk_part : nullptr;
+    QP_CHECK(launch_term(cur, e));
+    if (e.check_partials)
+      QP_CHECK(qp::launch_reduce_triples(ctx->stream, w->chk_part, qp::spmv_grid_size(A), w->chk_out + 3 * (m - 1), &ctx->stats));
+    if (m == 1) {
+      sc.c *= 2.0;  // :184
+      prev = P;
+      cur = B;
+    } else {
+      std::swap(cur, prev);      // prev's buffer now holds v_m: it is gathered next
+    }
+  }
+  if (result != P)
+    QP_HIP(hipMemcpyAsync(P, result, (size_t)psi->n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
+  return QP_OK;
+}
+
 extern "C" {
 
 // ---------------------------------------------------------------------------
@@ -91,199 +236,32 @@ int qp_cheby_term(qp_operator* op, const qp_state* x, int64_t xoff, const qp_sta
   QP_TRY
   const bool skip = defer && defer->skip;
   if (!op || !x || (!acc_out && !skip)) return qp::fail(QP_E_BAD_ARG, "qp_cheby_term: NULL argument");
-  if (defer && !skip && (defer->n_defer < 0 || defer->n_defer > 2 || (defer->n_defer > 0 && !v0 && (defer->n_defer == 2 || !acc_in))))
-    return qp::fail(QP_E_BAD_ARG, "qp_cheby_term: deferred accumulation needs v0");
-  const int64_t nr = op->A.nrows;
-  if (x->n != op->A.ncols || xoff < 0 || xoff + nr > x->n) return qp::fail(QP_E_BAD_ARG, "qp_cheby_term: x shape / offset mismatch");
-  if ((v0 && v0->n != nr) || (vout && vout->n != nr) || (acc_in && acc_in->n != nr) || (acc_out && acc_out->n != nr))
-    return qp::fail(QP_E_BAD_ARG, "qp_cheby_term: local vector length mismatch");
+  qp::ChebyEpi e;
+  QP_CHECK(cheby_term_args("qp_cheby_term", op, x, xoff, v0, vout, acc_in, acc_out, c, beta, a_prev, a, phase, defer, &e));
   auto overlaps = [&](const qp_state* s) { return s && s->d < x->d + x->n && x->d < s->d + s->n; };
   if (overlaps(vout) || overlaps(acc_out)) return qp::fail(QP_E_BAD_ARG, "qp_cheby_term: outputs must not overlap the gathered x");
   QP_CHECK(use(op->ctx));
-  qp::ChebyEpi e;
-  e.xloc = x->d + xoff;
-  e.v0 = v0 ? v0->d : nullptr;
-  e.vout = vout ? vout->d : nullptr;
-  e.acc_in = (acc_in && !skip) ? acc_in->d : nullptr;
-  e.acc_out = (acc_out && !skip) ? acc_out->d : nullptr;
-  e.c = d2(c);
-  e.beta = beta;
-  e.a_prev = a_prev;
-  e.a = a;
-  e.phase = d2(phase);
-  e.apply_phase = !(phase.re == 1.0 && phase.im == 0.0);
-  e.check_partials = nullptr;
-  set_defer(e, defer);
   return qp::launch_spmv_cheby(op->ctx->stream, op->A, x->d, e, &op->ctx->stats);
   QP_CATCH
-}
-
-// Does a whole-operator cheby! of `op` take the two-term strip walk (kernels_walk2.hip) under the context's knobs?  Beyond the
-// Infinity Cache only (inside it the one-term walk is not bound by the value stream), and only when a wavefront's strip column is
-// long enough for the 2 K steps a segment runs in before its first z to be a small part of it.
-static bool walk2_wanted(const qp_operator* op) {
-  const qp::Tuning& tun = op->ctx->tun;
-  const qp::WalkPlan& Q = op->walk2;
-  const DevMatrix& A = op->A;
-  if (!Q.valid || tun.walk_pair == 0 || !tun.hrb_walk || (tun.rbcsr_variant & 31) != 15 || A.walk != &op->walk || !op->walk.valid) return false;
-  if (op->walk.R1 - op->walk.W0 < tun.walk_min_blocks) return false;
-  if (tun.walk_pair == 1) return true;
-  const double footprint = (double)(Q.z0 + Q.nn + Q.K) * kRB * (double)A.nblocks * (A.vals_r ? 8.0 : 16.0) + 64.0 * (double)A.nrows;
-  if (footprint <= 230e6) return false;
-  const int W = kRB - 2 * Q.near[Q.nn - 1];
-  const int64_t S2 = (Q.g + W - 1) / W, Jz = ((Q.R1 - Q.W0) * (int64_t)kRB + Q.g - 1) / Q.g;
-  const int64_t waves = tun.walk_waves > 0 ? tun.walk_waves : 4 * (int64_t)qp::device_cu_count();
-  return Jz / std::max<int64_t>(1, waves / S2) >= 24;
 }
 
 int qp_operator_walk2_info(const qp_operator* op, int64_t out[8]) {
   QP_TRY
   if (!op || !out) return qp::fail(QP_E_BAD_ARG, "qp_operator_walk2_info: NULL argument");
   const bool on = walk2_wanted(op);
-  const int W = on ? kRB - 2 * op->walk2.near[op->walk2.nn - 1] : 0;
+  // the cut the launcher gets (kernels_walk2.hip: launch_hrb_walk2_cheby): rows of a chunk that form z, chunks per strip step,
+  // z steps per wavefront, segments per strip column
+  const qp::Walk2Cut C = on ? qp::walk2_cut(op->walk2, qp::walk_matrix(op->A), qp::walk_knobs(op->ctx->tun), qp::device_cu_count()) : qp::Walk2Cut();
   out[0] = on ? 1 : 0;
   out[1] = on ? op->walk2.W0 : 0;
   out[2] = on ? op->walk2.R1 : 0;
   out[3] = on ? op->walk2.n_edge : 0;
-  out[4] = W;
-  out[5] = on ? (op->walk2.g + W - 1) / W : 0;
-  out[6] = out[7] = 0;
-  if (on) {      // the cut of the walk (kernels_walk2.hip: launch_hrb_walk2_cheby): z steps per wavefront, segments per strip column
-    const qp::Tuning& tun = op->ctx->tun;
-    const int64_t Jz = ((op->walk2.R1 - op->walk2.W0) * (int64_t)kRB + op->walk2.g - 1) / op->walk2.g;
-    const int64_t waves = tun.walk_waves > 0 ? tun.walk_waves : 4 * (int64_t)qp::device_cu_count();
-    const int64_t L = (Jz + std::max<int64_t>(1, waves / out[5]) - 1) / std::max<int64_t>(1, waves / out[5]);
-    out[6] = L;
-    out[7] = (Jz + L - 1) / L;
-  }
+  out[4] = C.G.W;
+  out[5] = C.G.S2;
+  out[6] = C.G.L;
+  out[7] = C.G.nseg;
   return QP_OK;
   QP_CATCH
-}
-
-// the launches of one cheby! call (src/cheby.jl:171-211): n_coeffs - 1 fused mat-vec + term
-// kernels and, when the result does not land in Psi's buffer, one copy.
-// Term vectors: `cur` holds v_{m-1} (gathered by term m), `prev` holds v_{m-2}.  A one-term launch writes v_m over v_{m-2} in
-// place; a two-term launch (terms m and m + 1 in one pass over the matrix values, kernels_walk2.hip) writes v_m and v_{m+1} to two
-// vectors nobody reads meanwhile -- the neighbouring strip columns still gather from `cur` and `prev` -- so a step that takes pairs
-// rotates four vectors (Psi's, bufA, bufC, bufD) instead of two.
-static int cheby_step_launches(qp_cheby* w, qp_operator* op, qp_state* psi, const double* a, int n_coeffs, double beta,
-                               cplx c, cplx phase, bool check_normalization) {
-  qp_ctx* ctx = op->ctx;
-  const DevMatrix& A = op->A;
-  const int nterms = n_coeffs - 1;
-  const int nwg = qp::spmv_grid_size(A);
-  double2* P = psi->d;
-  double2* B = w->bufA;
-  double2* ACC = w->acc;
-  double2* result = nullptr;
-  std::vector<qp_acc_defer> sched((size_t)nterms);
-  acc_schedule(a, n_coeffs, ctx->tun.acc_defer != 0, sched.data());
-  bool pairs = !check_normalization && nterms >= 3 && w->bufC && w->bufD && walk2_wanted(op);   // (qp_cheby_step allocated the two vectors)
-  double2 *cur = P, *prev = nullptr;
-  double2* spare[2] = {w->bufC, w->bufD};      // the two vectors no term of the step is reading
-  bool updated = false;   // has any term written the accumulator yet?
-  auto fill = [&](qp::ChebyEpi& e, int m, const double2* x) {      // what every term's epilogue carries
-    e.a_prev = updated ? 0.0 : a[0];
-    set_defer(e, &sched[m - 1]);
-    if (sched[m - 1].skip) {
-      e.acc_in = nullptr;
-      e.acc_out = nullptr;
-    } else {
-      updated = true;
-    }
-    e.xloc = x;
-    e.c = d2(c);
-    e.beta = beta;
-    e.a = a[m];
-    e.phase = d2(phase);
-    e.apply_phase = (m == nterms) ? 1 : 0;
-  };
-  for (int m = 1; m <= nterms; ++m) {
-    const bool last = (m == nterms);
-    qp::ChebyEpi e;
-    if (m == 1) {
-      // v0 = Psi; Psi = a1 v0; v1 = c (H v0 - beta v0); Psi += a2 v1     :171-182
-      e.v0 = nullptr;
-      e.vout = last ? nullptr : B;
-      e.acc_in = nullptr;
-      e.acc_out = ACC;
-      result = ACC;
-    } else if (pairs && m + 1 <= nterms && !(sched[m - 1].skip == 0 && sched[m].skip == 0)) {
-      // terms m and m + 1 in one pass over the values: y = v_m -> spare[0], z = v_{m+1} -> spare[1]
-      const bool last2 = (m + 1 == nterms);
-      const bool updated_before = updated;
-      qp::ChebyEpi e1, e2;
-      e1.v0 = prev;
-      e1.vout = spare[0];
-      e1.acc_in = updated ? ACC : nullptr;
-      e1.acc_out = ACC;
-      e1.check_partials = nullptr;
-      fill(e1, m, cur);
-      e2.v0 = cur;
-      e2.vout = last2 ? nullptr : spare[1];
-      e2.acc_in = updated ? ACC : nullptr;
-      e2.acc_out = ACC;
-      e2.check_partials = nullptr;
-      fill(e2, m + 1, spare[0]);
-      bool launched = false;
-      {
-        const qp::ScopedRange mv_range(ctx->tun.roctx != 0 || qp::ranges_enabled_by_env(), "matrix-vector product");
-        QP_CHECK(qp::launch_hrb_walk2_cheby(ctx->stream, A, op->walk2, cur, e1, e2, ctx->tun, &launched));
-        if (launched) {
-          // term m + 1 of the blocks outside the two-term region: they read y of their neighbours, which the launch above wrote
-          qp::RowSet rs;
-          rs.block_map = op->walk2.edge_map;
-          rs.nmap = op->walk2.n_edge;
-          rs.count = false;
-          QP_CHECK(qp::launch_spmv_cheby(ctx->stream, A, spare[0], e2, &ctx->stats, &rs));
-          ctx->stats.n_launch++;
-          ctx->stats.n_matvec += 2;
-          ctx->stats.spmv_bytes += 2.0 * (20.0 * (double)A.nnz + 4.0 * (double)(A.nrows + 1) + 80.0 * (double)A.nrows);
-        }
-      }
-      if (launched) {
-        result = ACC;
-        double2* const y = spare[0];
-        double2* const z = spare[1];
-        spare[0] = cur;
-        spare[1] = prev;
-        prev = y;
-        cur = z;
-        ++m;
-        continue;
-      }
-      // not taken after all (the kernel's LDS opt-in was refused): this and every later term as one-term launches
-      updated = updated_before;
-      pairs = false;
-    }
-    if (m > 1) {
-      // v2 = c (H v1 - beta v1) + v0; Psi += a_i v2; rotate            :186-207
-      e.v0 = prev;                      // holds v0, overwritten in place by v2
-      e.vout = last ? nullptr : prev;
-      e.acc_in = updated ? ACC : nullptr;
-      e.acc_out = (last && cur != P && !pairs) ? P : ACC;  // P may be written only while it is not gathered
-      result = e.acc_out;
-    }
-    fill(e, m, cur);
-    // the reference checks terms i >= 3 only (inside the loop at :186)
-    e.check_partials = (check_normalization && m >= 2) ? w->chk_part : nullptr;
-    {
-      const qp::ScopedRange mv_range(ctx->tun.roctx != 0 || qp::ranges_enabled_by_env(), "matrix-vector product");   // src/cheby.jl:175, :189
-      QP_CHECK(qp::launch_spmv_cheby(ctx->stream, A, cur, e, &ctx->stats));
-    }
-    if (e.check_partials)
-      QP_CHECK(qp::launch_reduce_triples(ctx->stream, w->chk_part, nwg, w->chk_out + 3 * (m - 1), &ctx->stats));
-    if (m == 1) {
-      c *= 2.0;  // :184
-      prev = P;
-      cur = B;
-    } else {
-      std::swap(cur, prev);      // prev's buffer now holds v_m: it is gathered next
-    }
-  }
-  if (result != P)
-    QP_HIP(hipMemcpyAsync(P, result, (size_t)psi->n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
-  return QP_OK;
 }
 
 int qp_cheby_step(qp_cheby* w, qp_operator* op, qp_state* psi, const double* a, int n_coeffs, double Delta,
@@ -292,22 +270,19 @@ int qp_cheby_step(qp_cheby* w, qp_operator* op, qp_state* psi, const double* a, 
   if (!w || !op || !psi || !a) return qp::fail(QP_E_BAD_ARG, "qp_cheby_step: NULL argument");
   if (op->A.nrows != op->A.ncols || psi->n != op->A.nrows || w->n != psi->n)
     return qp::fail(QP_E_BAD_ARG, "qp_cheby_step: shape mismatch");
-  // @assert abs(dt) ~ abs(wrk.dt)   (isapprox, rtol = sqrt(eps))   src/cheby.jl:157
-  {
-    const double x = std::fabs(dt), y = std::fabs(wrk_dt);
-    if (!(std::fabs(x - y) <= 1.4901161193847656e-08 * std::max(x, y)))
-      return qp::fail(QP_E_DT_MISMATCH, "wrk was initialized for dt=%g, not dt=abs(%g)", wrk_dt, dt);
-  }
+  if (!cheby_dt_matches(dt, wrk_dt)) return qp::fail(QP_E_DT_MISMATCH, "wrk was initialized for dt=%g, not dt=abs(%g)", wrk_dt, dt);
   if (n_coeffs < 2) return qp::fail(QP_E_TOO_FEW_COEFFS, "Need at least 2 Chebychev coefficients");
   if (!(Delta > 0)) return qp::fail(QP_E_BAD_ARG, "Delta must be positive");
   qp_ctx* ctx = op->ctx;
   QP_CHECK(use(ctx));
   const qp::ScopedRange step_range(ctx->tun.roctx != 0 || qp::ranges_enabled_by_env(), "prop_step!");   // src/cheby_propagator.jl:349
-  const double beta = (Delta / 2) + E_min;                        // :156
-  cplx c = (dt > 0) ? cplx(0, -2.0) / Delta : cplx(0, 2.0) / Delta;  // :158-162
-  const cplx phase = std::exp(cplx(0, -1) * beta * dt);            // :211
+  const ChebyScalars sc(Delta, E_min, dt);
   const int nterms = n_coeffs - 1;
   const DevMatrix& A = op->A;
+  auto launch_term = [&](const double2* x, const qp::ChebyEpi& e) -> int {
+    const qp::ScopedRange mv_range(ctx->tun.roctx != 0 || qp::ranges_enabled_by_env(), "matrix-vector product");   // src/cheby.jl:175, :189
+    return qp::launch_spmv_cheby(ctx->stream, A, x, e, &ctx->stats);
+  };
   const int nwg = qp::spmv_grid_size(A);
   if (check_normalization) {
     if (w->chk_wg < nwg) {
@@ -372,7 +347,7 @@ int qp_cheby_step(qp_cheby* w, qp_operator* op, qp_state* psi, const double* a, 
       hipGraph_t graph = nullptr;
       const Stats before = ctx->stats;
       QP_HIP(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-      const int rc = cheby_step_launches(w, op, psi, a, n_coeffs, beta, c, phase, false);
+      const int rc = cheby_step_launches(w, op, psi, a, n_coeffs, sc, false, false, launch_term);
       w->gstats = Stats();
       w->gstats.n_matvec = ctx->stats.n_matvec - before.n_matvec;
       w->gstats.n_launch = ctx->stats.n_launch - before.n_launch;
@@ -398,7 +373,7 @@ int qp_cheby_step(qp_cheby* w, qp_operator* op, qp_state* psi, const double* a, 
       w->gpending = key;
     }
   }
-  if (!done) QP_CHECK(cheby_step_launches(w, op, psi, a, n_coeffs, beta, c, phase, check_normalization != 0));
+  if (!done) QP_CHECK(cheby_step_launches(w, op, psi, a, n_coeffs, sc, check_normalization != 0, false, launch_term));
   ctx->stats.n_cheby_steps++;
   if (check_normalization && nterms >= 2) {
     std::vector<double> h((size_t)3 * nterms);
@@ -426,11 +401,7 @@ int qp_cheby_step_batched(qp_cheby* w, qp_operator* op, qp_state* psi, int batch
   if (op->A.nrows != op->A.ncols || psi->n != n * batch || w->n != psi->n)
     return qp::fail(QP_E_BAD_ARG, "qp_cheby_step_batched: shape mismatch (operator %lld, batch %d, panel %lld)",
                     (long long)n, batch, (long long)psi->n);
-  {
-    const double x = std::fabs(dt), y = std::fabs(wrk_dt);
-    if (!(std::fabs(x - y) <= 1.4901161193847656e-08 * std::max(x, y)))
-      return qp::fail(QP_E_DT_MISMATCH, "wrk was initialized for dt=%g, not dt=abs(%g)", wrk_dt, dt);
-  }
+  if (!cheby_dt_matches(dt, wrk_dt)) return qp::fail(QP_E_DT_MISMATCH, "wrk was initialized for dt=%g, not dt=abs(%g)", wrk_dt, dt);
   if (n_coeffs < 2) return qp::fail(QP_E_TOO_FEW_COEFFS, "Need at least 2 Chebychev coefficients");
   if (!(Delta > 0)) return qp::fail(QP_E_BAD_ARG, "Delta must be positive");
   qp_ctx* ctx = op->ctx;
@@ -446,69 +417,16 @@ int qp_cheby_step_batched(qp_cheby* w, qp_operator* op, qp_state* psi, int batch
   if (rows_kernel && ctx->tun.spmm_rw < 0) QP_CHECK(operator_spmm_tiles(op, &tiles));
   if (rows_kernel && !tiles) QP_CHECK(operator_spmm_order(op, batch, &order));
 
-  const double beta = (Delta / 2) + E_min;
-  cplx c = (dt > 0) ? cplx(0, -2.0) / Delta : cplx(0, 2.0) / Delta;
-  const cplx phase = std::exp(cplx(0, -1) * beta * dt);
-  const int nterms = n_coeffs - 1;
-  double2* P = psi->d;
-  double2* B = w->bufA;
-  double2* ACC = w->acc;
-  double2* result = nullptr;
-  std::vector<qp_acc_defer> sched((size_t)nterms);
-  acc_schedule(a, n_coeffs, ctx->tun.acc_defer != 0, sched.data());
-  bool updated = false;
-  for (int m = 1; m <= nterms; ++m) {   // same buffer rotation as qp_cheby_step, element = (row, state)
-    const bool last = (m == nterms);
-    qp::ChebyEpi e;
-    const double2* x;
-    if (m == 1) {
-      x = P;
-      e.v0 = nullptr;
-      e.vout = last ? nullptr : B;
-      e.acc_in = nullptr;
-      e.acc_out = ACC;
-      result = ACC;
-    } else {
-      double2* xb = (m % 2 == 0) ? B : P;
-      double2* ob = (m % 2 == 0) ? P : B;
-      x = xb;
-      e.v0 = ob;
-      e.vout = last ? nullptr : ob;
-      e.acc_in = updated ? ACC : nullptr;
-      e.acc_out = (last && xb == B) ? P : ACC;
-      result = e.acc_out;
-    }
-    e.a_prev = updated ? 0.0 : a[0];
-    set_defer(e, &sched[(size_t)m - 1]);
-    if (sched[(size_t)m - 1].skip) {
-      e.acc_in = nullptr;
-      e.acc_out = nullptr;
-    } else {
-      updated = true;
-    }
-    e.xloc = x;
-    e.c = d2(c);
-    e.beta = beta;
-    e.a = a[m];
-    e.phase = d2(phase);
-    e.apply_phase = last ? 1 : 0;
-    e.check_partials = nullptr;
-    bool walked = false;
-    if (dense) {
-      QP_CHECK(qp::launch_dense_zgemm_cheby(ctx->stream, op->A, x, batch, e, &ctx->stats));
-      walked = true;
-    }
-    if (!walked && tiles) {
-      QP_CHECK(qp::launch_spmm_tile_cheby(ctx->stream, op->m_rowptr, op->m_cols, op->m_vals, x, n, op->A.nnz, batch, e, ctx->tun,
-                                          *tiles, &ctx->stats));
-      walked = true;
-    }
-    if (!walked)
-      QP_CHECK(qp::launch_spmm_cheby(ctx->stream, op->m_rowptr, op->m_cols, op->m_vals, x, n, op->A.nnz, batch, e,
-                                     ctx->tun, rows_kernel, order, &ctx->stats));
-    if (m == 1) c *= 2.0;
-  }
-  if (result != P) QP_HIP(hipMemcpyAsync(P, result, (size_t)psi->n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
+  // the term loop and buffer rotation of qp_cheby_step, element = (row, state)
+  auto launch_term = [&](const double2* x, const qp::ChebyEpi& e) -> int {
+    if (dense) return qp::launch_dense_zgemm_cheby(ctx->stream, op->A, x, batch, e, &ctx->stats);
+    if (tiles)
+      return qp::launch_spmm_tile_cheby(ctx->stream, op->m_rowptr, op->m_cols, op->m_vals, x, n, op->A.nnz, batch, e, ctx->tun,
+                                        *tiles, &ctx->stats);
+    return qp::launch_spmm_cheby(ctx->stream, op->m_rowptr, op->m_cols, op->m_vals, x, n, op->A.nnz, batch, e, ctx->tun,
+                                 rows_kernel, order, &ctx->stats);
+  };
+  QP_CHECK(cheby_step_launches(w, op, psi, a, n_coeffs, ChebyScalars(Delta, E_min, dt), false, true, launch_term));
   ctx->stats.n_cheby_steps++;
   return QP_OK;
   QP_CATCH
@@ -673,30 +591,12 @@ int qp_cheby_term_split(qp_operator* op, qp_split* sp, void* boundary_stream, in
   const bool skip = defer && defer->skip;
   if (!op || !sp || sp->op != op || !boundary_stream || !x || (!acc_out && !skip))
     return qp::fail(QP_E_BAD_ARG, "qp_cheby_term_split: bad arguments");
-  if (defer && !skip && (defer->n_defer < 0 || defer->n_defer > 2 || (defer->n_defer > 0 && !v0 && (defer->n_defer == 2 || !acc_in))))
-    return qp::fail(QP_E_BAD_ARG, "qp_cheby_term_split: deferred accumulation needs v0");
-  const int64_t nr = op->A.nrows;
-  if (x->n != op->A.ncols || xoff < 0 || xoff + nr > x->n) return qp::fail(QP_E_BAD_ARG, "qp_cheby_term_split: x shape / offset mismatch");
-  if ((v0 && v0->n != nr) || (vout && vout->n != nr) || (acc_in && acc_in->n != nr) || (acc_out && acc_out->n != nr))
-    return qp::fail(QP_E_BAD_ARG, "qp_cheby_term_split: local vector length mismatch");
+  qp::ChebyEpi e;
+  QP_CHECK(cheby_term_args("qp_cheby_term_split", op, x, xoff, v0, vout, acc_in, acc_out, c, beta, a_prev, a, phase, defer, &e));
   if (slab && slab->n < sp->nsend) return qp::fail(QP_E_BAD_ARG, "qp_cheby_term_split: slab too small");
   qp_ctx* ctx = op->ctx;
   QP_CHECK(use(ctx));
   hipStream_t S_c = ctx->stream, S_x = (hipStream_t)boundary_stream;
-  qp::ChebyEpi e;
-  e.xloc = x->d + xoff;
-  e.v0 = v0 ? v0->d : nullptr;
-  e.vout = vout ? vout->d : nullptr;
-  e.acc_in = (acc_in && !skip) ? acc_in->d : nullptr;
-  e.acc_out = (acc_out && !skip) ? acc_out->d : nullptr;
-  e.c = d2(c);
-  e.beta = beta;
-  e.a_prev = a_prev;
-  e.a = a;
-  e.phase = d2(phase);
-  e.apply_phase = !(phase.re == 1.0 && phase.im == 0.0);
-  e.check_partials = nullptr;
-  set_defer(e, defer);
   qp::RowSet rb{sp->bmap_boundary, sp->n_boundary, false};
   qp::RowSet ri{sp->bmap_interior, sp->n_interior, true};
   if (sp->walk.valid) {   // lattice operator: the interior as a strip walk; CUs beyond the edge workgroups' stay free (knob) for
@@ -769,16 +669,13 @@ static int propagate_cheby_small(qp_operator* op, qp_state* psi, const qp_prop_s
   if (spec->n_coeffs < 2) return qp::fail(QP_E_TOO_FEW_COEFFS, "Need at least 2 Chebychev coefficients");
   if (!(spec->Delta > 0)) return qp::fail(QP_E_BAD_ARG, "Delta must be positive");
   for (int k = 0; k < nsteps; ++k) {
-    const double x = std::fabs(dts[k]), y = std::fabs(spec->wrk_dt);   // src/cheby.jl:157
-    if (!(std::fabs(x - y) <= 1.4901161193847656e-08 * std::max(x, y)))
+    if (!cheby_dt_matches(dts[k], spec->wrk_dt))
       return qp::fail(QP_E_DT_MISMATCH, "wrk was initialized for dt=%g, not dt=abs(%g)", spec->wrk_dt, dts[k]);
     if ((dts[k] > 0) != (dts[0] > 0)) return qp::fail(QP_E_BAD_ARG, "qp_propagate: time steps change sign");
   }
   QP_CHECK(operator_csr_mirror(op));
   for (int o = 0; o < nobs; ++o) QP_CHECK(operator_csr_mirror(observables[o]));
-  const double dt = dts[0];
-  const double beta = (spec->Delta / 2) + spec->E_min;
-  const cplx c = (dt > 0) ? cplx(0, -2.0) / spec->Delta : cplx(0, 2.0) / spec->Delta;
+  const ChebyScalars sc(spec->Delta, spec->E_min, dts[0]);
 
   a.n = n;
   a.nnz = op->A.nnz;
@@ -791,9 +688,9 @@ static int propagate_cheby_small(qp_operator* op, qp_state* psi, const qp_prop_s
   a.scale = d2(op->scale);
   a.nsteps = nsteps;
   a.n_coeffs = spec->n_coeffs;
-  a.c = d2(c);
-  a.beta = beta;
-  a.phase = d2(std::exp(cplx(0, -1) * beta * dt));
+  a.c = d2(sc.c);
+  a.beta = sc.beta;
+  a.phase = d2(sc.phase);
   a.psi = psi->d;
   a.nobs = nobs;
   a.check = spec->check_normalization ? 1 : 0;

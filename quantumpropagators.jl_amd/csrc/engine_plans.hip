@@ -8,7 +8,7 @@
 
 #include "engine_host.h"
 
-// Strip-walk plan of a Hermitian-packed lattice operator (device.h: WalkPlan; kernels_walk.hip).  Looks, in the union
+// Strip-walk plan of a Hermitian-packed lattice operator (walk_geometry.h: WalkPlan; kernels_walk.hip).  Looks, in the union
 // pattern itself, for the longest run of row blocks in which every row has the same list of column distances, checks that
 // the list has the shape the walk needs -- [-K g .. -g] [-d_nn .. -d_1] [0]? [d_1 .. d_nn] [g .. K g], g a multiple of 64
 // rows -- and that the upper values of the run's blocks lie at equal strides.  With one stencil on every row of the run the

@@ -288,11 +288,8 @@ int qp_sharded_cheby_step(qp_sharded_cheby* s, const double* a, int n_coeffs, do
   QP_CHECK(use(ctx));
   const int64_t nloc = s->nloc;
   const int nterms = n_coeffs - 1;
-  const double beta = (Delta / 2) + E_min;                               // src/cheby.jl:156
-  cplx c = (dt > 0) ? cplx(0, -2.0) / Delta : cplx(0, 2.0) / Delta;      // :158-162
-  const cplx phase = std::exp(cplx(0, -1) * beta * dt);                  // :211
-  std::vector<qp_acc_defer> sched((size_t)nterms);
-  acc_schedule(a, n_coeffs, ctx->tun.acc_defer != 0, sched.data());
+  ChebyScalars sc(Delta, E_min, dt);
+  ChebyAcc acc(a, n_coeffs, ctx->tun.acc_defer != 0);
   const bool exchanging = d.M > 0;
   const bool overlap = d.split != nullptr;
   hipStream_t S_c = ctx->stream;
@@ -358,30 +355,28 @@ int qp_sharded_cheby_step(qp_sharded_cheby* s, const double* a, int n_coeffs, do
     QP_HIP(hipStreamWaitEvent(S_x, s->ev_main, 0));
   }
   QP_CHECK(exchange(0, false));
-  bool updated = false;
   bool result_in_acc = true;
   for (int m = 1; m <= nterms; ++m) {
     const bool last = (m == nterms);
     const int xi = (m % 2 == 1) ? 0 : 1, oi = 1 - xi;
-    const qp_acc_defer& df = sched[(size_t)m - 1];
-    const qp_c128 cc{c.real(), c.imag()};
-    const qp_c128 ph = last ? qp_c128{phase.real(), phase.imag()} : qp_c128{1.0, 0.0};
+    const ChebyAcc::Term t = acc.term(m);
+    const qp_acc_defer& df = *t.defer;
+    const qp_c128 cc{sc.c.real(), sc.c.imag()};
+    const qp_c128 ph = last ? qp_c128{sc.phase.real(), sc.phase.imag()} : qp_c128{1.0, 0.0};
     const qp_state* v0 = (m == 1) ? nullptr : &xloc[oi];
     qp_state* vout = last ? nullptr : &xloc[oi];
-    const qp_state* acc_in = (updated && !df.skip) ? d.acc : nullptr;
+    const qp_state* acc_in = t.acc_in ? d.acc : nullptr;
     // the state buffer X0 may be written only while it is not being gathered
     qp_state* out = (m > 1 && last && xi == 1) ? &xloc[0] : d.acc;
     if (!df.skip && m > 1) result_in_acc = (out == d.acc);
-    const double a_prev = updated ? 0.0 : a[0];
     if (overlap) {
       QP_CHECK(qp_cheby_term_split(d.op, d.split, (void*)S_x, m == 1 ? 1 : 0, X[xi], 0, v0, vout, acc_in,
-                                   df.skip ? nullptr : out, last ? nullptr : d.slab, cc, beta, a_prev, a[m], ph, &df));
+                                   df.skip ? nullptr : out, last ? nullptr : d.slab, cc, sc.beta, t.a_prev, a[m], ph, &df));
     } else {
-      QP_CHECK(qp_cheby_term(d.op, X[xi], 0, v0, vout, acc_in, df.skip ? nullptr : out, cc, beta, a_prev, a[m], ph, &df));
+      QP_CHECK(qp_cheby_term(d.op, X[xi], 0, v0, vout, acc_in, df.skip ? nullptr : out, cc, sc.beta, t.a_prev, a[m], ph, &df));
     }
-    updated = updated || !df.skip;
     if (!last) QP_CHECK(exchange(oi, overlap));
-    if (m == 1) c *= 2.0;                                                 // :184
+    if (m == 1) sc.c *= 2.0;                                               // :184
   }
   if (overlap) {   // join back: later work on the main stream sees everything the side stream did
     QP_HIP(hipEventRecord(s->ev_side, S_x));

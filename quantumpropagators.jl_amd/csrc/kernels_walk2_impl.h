@@ -30,13 +30,9 @@
 // Both row sums are the one-term walk's (lower slots then upper slots in storage order, two interleaved partial sums) and both
 // epilogues are ChebyOp's: bit-identical to one-term launches (tests/test_gpu_walk2.py).
 #pragma once
-#include <atomic>
-
 #include "kernels_walk_impl.h"
 
 namespace qp {
-
-constexpr int kWalk2Waves = 4;   // wavefronts per workgroup = per compute unit: one per SIMD
 
 template <int NN, int K>
 struct Walk2Lds {
@@ -45,14 +41,6 @@ struct Walk2Lds {
   static constexpr int kFifo = K * K + K * (K + 1) / 2;        // far slot m: K + m entries of 64
   static constexpr int kPerWave = kWin + kRB * kFifo;
   static constexpr size_t kBytesPerWave = sizeof(double2) * (size_t)kPerWave;
-};
-
-struct Walk2Geom {
-  int L = 0, nseg = 0, ntask = 0, n_walk_wg = 0;
-  int S2 = 0;          // column chunks per strip step: ceil(g / W)
-  int W = 0;           // rows of a chunk that form z: 64 - 2 d_max
-  int64_t xlast = 0;   // last element of x
-  int64_t vend = 0;    // first row beyond the lattice run (values at the run's strides exist below it)
 };
 
 template <int NU>
@@ -337,17 +325,8 @@ static bool launch2_instance(hipStream_t s, const VT* uvals, const double2* x, c
                              const HrbArrays& H, int64_t nrows, const ChebyOp& op1, const ChebyOp& op2) {
   constexpr size_t lds = Walk2Lds<NN, K>::kBytesPerWave * kWalk2Waves;
   static_assert(lds <= 160 * 1024, "four wavefronts' windows and FIFOs fit the compute unit's LDS");
-  auto kern = &hrb_walk2_kernel<VT, NN, K, Z0, NTM>;
-  static std::atomic<unsigned char> opted[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  unsigned char st = opted[dev].load(std::memory_order_acquire);
-  if (st == 0) {
-    st = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? 1 : 2;
-    if (st == 2) (void)hipGetLastError();
-    opted[dev].store(st, std::memory_order_release);
-  }
-  if (st != 1) return false;
+  constexpr auto kern = &hrb_walk2_kernel<VT, NN, K, Z0, NTM>;
+  if (!lds_opt_in<kern>(lds)) return false;
   hipLaunchKernelGGL(kern, dim3((unsigned)G.n_walk_wg), dim3(64 * kWalk2Waves), lds, s, uvals, x, P, G, H, nrows, op1, op2);
   return true;
 }

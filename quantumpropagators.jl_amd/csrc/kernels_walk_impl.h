@@ -9,7 +9,7 @@
 // only the first 8 KiB and two of the vector streams come from HBM.  Beyond the Infinity Cache the L1's miss queue, not
 // HBM, is what is full (profiles/r03/hrb_n22_pmc_diag.txt: texture addresser busy 85 %, the L1 stalled on its pending
 // misses 58 % of the launch, 209 L1 -> L2 requests per block, 83 in flight per CU).  On a lattice all of that re-read
-// data is data the SAME wavefront would load anyway if it walked down a strip column (see WalkPlan in device.h):
+// data is data the SAME wavefront would load anyway if it walked down a strip column (see WalkPlan in walk_geometry.h):
 //   * x[r + m g]              = the row-local element of the block m steps away           -> register ring, 1 load/step
 //   * conj H[r - m g, r]      = the far upper value streamed m steps ago                  -> FIFO in LDS, 0 loads
 //   * x[r +- d], conj H[r - d, r] (d <= 16) = lane shifts of the block's own element / near values
@@ -37,28 +37,27 @@ struct HrbArrays {   // what the per-block path of the edge blocks reads
   const int4* lpos4;
 };
 
-struct WalkGeom {
-  int L = 0;           // steps per wavefront
-  int nseg = 0;        // segments of L steps per strip column
-  int n_walk_wg = 0;
-  int ntask = 0;       // wavefronts of the walk (n_walk_wg x wavefronts per workgroup)
-  // Edge blocks (outside the walkable run), two schemes:
-  //  * beside the walk (n_edge_wg > 0): workgroups of their own at the head of the grid, one block per wavefront, while
-  //    every workgroup of the launch still finds room on the chip at once -- the walk is cut so that it does (768
-  //    wavefronts inside the Infinity Cache, 8 per CU on all but the CUs the edge workgroups take beyond it);
-  //  * inside the walk (n_edge_wg == 0; knob walk_waves / walk_dbg): edge block i goes to wavefront i, BEFORE its walk
-  //    (edge_last: after), and the segments of those wavefronts are `edge_steps` steps shorter -- a block on the per-block
-  //    path is three dependent rounds of loads, a step of the walk about one -- so that every wavefront finishes at
-  //    about the same time.  (As leading workgroups of a launch that fills every CU they cost 5-6 us: whichever compute
-  //    units ran them started their walk that much later.)
-  int edge_segs = 0;   // segments 0 .. edge_segs - 1 are the shorter ones
-  int edge_steps = 0;
-  int edge_last = 0;
-  int64_t xlast = 0;   // last element of x (columns of a row-partitioned operator run beyond its rows: the halo slabs)
-  int n_edge_wg = 0;
-};
+inline HrbArrays hrb_arrays(const DevMatrix& A) {
+  return HrbArrays{A.bptr, A.cmeta, reinterpret_cast<const char*>(A.cols), A.lptr, A.lcmeta,
+                   reinterpret_cast<const char*>(A.lcols), reinterpret_cast<const int4*>(A.lpos)};
+}
 
-constexpr int kWalkWaves = 8;   // most wavefronts (adjacent strip columns) per workgroup; the launch may use fewer (knob walk_wg)
+// Dynamic LDS beyond the 64 KB a launch gets without asking: opt in once per kernel instance (the template argument) AND
+// device (a process may hold contexts on several GPUs); 0 = not tried, 1 = granted, 2 = refused (false: the caller then
+// takes the per-block kernel)
+template <auto Kern>
+static bool lds_opt_in(size_t bytes) {
+  static std::atomic<unsigned char> opted[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+  unsigned char st = opted[dev].load(std::memory_order_acquire);
+  if (st == 0) {
+    st = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 1 : 2;
+    if (st == 2) (void)hipGetLastError();
+    opted[dev].store(st, std::memory_order_release);
+  }
+  return st == 1;
+}
 
 // One row block by the per-block rules of hrb_spmv_kernel (same sums), arranged for LATENCY: a wavefront of the walk
 // takes its edge block alone, so the block is three dependent rounds of loads -- block pointers; column sections,
@@ -550,19 +549,8 @@ static bool launch_instance(hipStream_t s, dim3 grid, const VT* uvals, const dou
   const int ws = G.ntask / std::max(G.n_walk_wg, 1);      // wavefronts per workgroup of this launch
   const size_t lds = WalkLds<NN, K, FD>::kBytesPerWave * (size_t)ws;
   constexpr size_t lds_max = WalkLds<NN, K, FD>::kBytesPerWave * kWalkWaves;
-  auto kern = &hrb_walk_kernel<VT, NN, K, Z0, NTM, XL, FD>;
-  // more than the 64 KB a launch gets without asking: opt in once per kernel instance AND device (a process may hold
-  // contexts on several GPUs); 0 = not tried, 1 = granted, 2 = refused (the caller then takes the per-block kernel)
-  static std::atomic<unsigned char> opted[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  unsigned char st = opted[dev].load(std::memory_order_acquire);
-  if (st == 0) {
-    st = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) == hipSuccess ? 1 : 2;
-    if (st == 2) (void)hipGetLastError();
-    opted[dev].store(st, std::memory_order_release);
-  }
-  if (st != 1) return false;
+  constexpr auto kern = &hrb_walk_kernel<VT, NN, K, Z0, NTM, XL, FD>;
+  if (!lds_opt_in<kern>(lds_max)) return false;
   hipLaunchKernelGGL(kern, grid, dim3(64 * ws), lds, s, uvals, x, P, G, H, nrows, op, sy);
   return true;
 }

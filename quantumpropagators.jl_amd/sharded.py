@@ -370,8 +370,6 @@ class ShardedCheby:
             self.native.step(self.coeffs, self.Delta, self.E_min, -self.dt if backward else self.dt)
             self.n_exchanges += len(self.coeffs) - 1 if self.exchanging else 0
             return None
-        if self.split is not None:
-            return self._step_overlapped(backward)
         a = self.coeffs
         Delta = self.Delta
         dt = -self.dt if backward else self.dt
@@ -380,81 +378,47 @@ class ShardedCheby:
         phase = np.exp(-1j * beta * dt)
         nterms = len(a) - 1
         be, op = self.be, self.op
-        self._exchange(0)
-        result_in_acc = True
-        updated = False                 # has a term written the accumulator yet?
-        for m in range(1, nterms + 1):
-            last = m == nterms
-            xi, oi = (0, 1) if m % 2 == 1 else (1, 0)
-            x, oloc = self.Xfull[xi], self.Xloc[oi]
-            ph = phase if last else 1.0
-            d = self.sched[m - 1]
-            acc_in = self.acc if (updated and not d.skip) else None
-            a_prev = 0.0 if updated else a[0]
-            if m == 1:
-                be.term(op, x, 0, None, None if last else oloc, None, None if d.skip else self.acc, c, beta, a_prev,
-                        a[1], ph, d)
-            else:
-                # the state buffer X[0] may be written only while it is not being gathered
-                out = self.Xloc[0] if (last and xi == 1) else self.acc
-                be.term(op, x, 0, oloc, None if last else oloc, acc_in, None if d.skip else out, c, beta, a_prev,
-                        a[m], ph, d)
-                result_in_acc = out is self.acc
-            updated = updated or not d.skip
-            if not last:
-                self._exchange(oi)
-            if m == 1:
-                c = 2 * c
-        if result_in_acc:
-            self.X[0][: 2 * self.nloc].copy_(self.acc_t)
-
-    def _step_overlapped(self, backward=False):
-        """Same arithmetic as :meth:`step`; per term the boundary row blocks run on the side
-        stream, immediately followed there by the all-gather of their packed output, while
-        the interior row blocks (which read no ghost slot) run on the main stream."""
-        a = self.coeffs
-        Delta = self.Delta
-        dt = -self.dt if backward else self.dt
-        beta = Delta / 2 + self.E_min
-        c = (-2j / Delta) if dt > 0 else (2j / Delta)
-        phase = np.exp(-1j * beta * dt)
-        nterms = len(a) - 1
-        be, op, side = self.be, self.op, self.side
-        be.join(side)
-        # the side stream is the thread's current stream for the whole step, so that the
-        # collectives order themselves against it without a per-term stream context switch;
-        # the interior launches go to the context's (main) stream explicitly
-        main = be.current_stream()
-        be.set_stream(side)
+        # Overlapped schedule (a boundary / interior split exists): same arithmetic; per term the boundary row blocks run on
+        # the side stream, immediately followed there by the all-gather of their packed output, while the interior row blocks
+        # (which read no ghost slot) run on the main stream.  The side stream is the thread's current stream for the whole
+        # step, so that the collectives order themselves against it without a per-term stream context switch; the interior
+        # launches go to the context's (main) stream explicitly
+        overlap = self.split is not None
+        if overlap:
+            side = self.side
+            be.join(side)
+            main = be.current_stream()
+            be.set_stream(side)
         try:
             self._exchange(0)
             result_in_acc = True
-            updated = False
+            updated = False                 # has a term written the accumulator yet?
             for m in range(1, nterms + 1):
                 last = m == nterms
                 xi, oi = (0, 1) if m % 2 == 1 else (1, 0)
                 x, oloc = self.Xfull[xi], self.Xloc[oi]
-                ph = phase if last else 1.0
-                slab = None if last else self.slab_state
                 d = self.sched[m - 1]
-                acc_in = self.acc if (updated and not d.skip) else None
-                a_prev = 0.0 if updated else a[0]
-                if m == 1:
-                    be.term_split(op, self.split, side, True, x, 0, None, None if last else oloc, None,
-                                  None if d.skip else self.acc, slab, c, beta, a_prev, a[1], ph, d)
+                # the state buffer X[0] may be written only while it is not being gathered
+                out = self.Xloc[0] if (m > 1 and last and xi == 1) else self.acc
+                args = (x, 0, None if m == 1 else oloc, None if last else oloc,
+                        self.acc if (updated and not d.skip) else None, None if d.skip else out)
+                scal = (c, beta, 0.0 if updated else a[0], a[m], phase if last else 1.0, d)
+                if overlap:
+                    be.term_split(op, self.split, side, m == 1, *args, None if last else self.slab_state, *scal)
                 else:
-                    out = self.Xloc[0] if (last and xi == 1) else self.acc
-                    be.term_split(op, self.split, side, False, x, 0, oloc, None if last else oloc, acc_in,
-                                  None if d.skip else out, slab, c, beta, a_prev, a[m], ph, d)
+                    be.term(op, *args, *scal)
+                if m > 1:
                     result_in_acc = out is self.acc
                 updated = updated or not d.skip
                 if not last:
-                    self._exchange(oi, packed=True)
+                    self._exchange(oi, packed=overlap)
                 if m == 1:
                     c = 2 * c
         finally:
-            be.set_stream(main)
-        be.join(side)
+            if overlap:
+                be.set_stream(main)
+        if overlap:
+            be.join(side)
         if result_in_acc:
             self.X[0][: 2 * self.nloc].copy_(self.acc_t)
 

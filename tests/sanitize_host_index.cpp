@@ -2,13 +2,17 @@
 // host before a kernel ever runs -- union pattern, Hermitian check, format choice, lattice completion, strip-walk plan, column
 // encodings (int32 / int16 / stencil / block map), Hermitian packing with transposed positions, column-blocked mirror, value
 // dictionary -- and the decoders of qp_operator_get_csr, compiled from the library's own sources (csrc/engine_core.hip,
-// csrc/engine_operator.hip, csrc/engine_plans.hip here; csrc/operator_layout.cpp and csrc/host_numerics.cpp beside it as
+// csrc/engine_operator.hip, csrc/engine_plans.hip here; csrc/operator_layout.cpp, csrc/walk_geometry.cpp and csrc/host_numerics.cpp beside it as
 // ordinary C++) with g++ against tests/hip_host_shim (device memory = heap memory, so the
 // sanitizer checks every copy into a "device" array against its allocation) and driven by a fuzz over the shapes that have bitten:
 // tall (5681 x 358: the round-4 GPU memory fault), wide, 1 row, fewer than 64 rows, empty rows, lattices, grids, spin chains.
 // Checked per case: the get_csr round trip reproduces the input exactly; EVERY stored slot of every row block -- real entries,
 // pads, the lanes beyond the last row -- decodes to a column inside the matrix; every pad carries the value zero in every term;
 // every transposed position of a Hermitian-packed operator is -1 (pad) or inside the value array.
+// For every operator with a strip-walk plan, the CUT of its launches (csrc/walk_geometry.cpp, the pure-host unit the launchers call) is
+// swept over chip sizes and knobs and checked against the kernels' own segment formulas: every strip step belongs to exactly one
+// segment, every edge block is reached, the launch fits the chip; and a table of named inputs (tests/walk_geometry_cases.h) pins
+// the numbers.
 // Built and run by tests/test_cabi_host.py::test_host_index_work_under_sanitizers (CPU only).
 // `--digest`: per case one line with the format, the scalar fields of the layout structs and a 64-bit FNV-1a hash over the
 // declared extent of every "device" array the operator owns -- two builds of the library lay operators out bit-identically iff
@@ -20,6 +24,7 @@
 #include "../quantumpropagators.jl_amd/csrc/engine_core.hip"
 #include "../quantumpropagators.jl_amd/csrc/engine_operator.hip"
 #include "../quantumpropagators.jl_amd/csrc/engine_plans.hip"
+#include "walk_geometry_cases.h"
 
 // ---- host stand-ins of the few launches the creation path makes (values only; no kernel runs in this build) ---------------
 namespace qp {
@@ -185,6 +190,148 @@ void print_digest(const qp_operator* op, const char* what) {
   std::printf("digest %s | format %d |%s | %016llx\n", what, A.format, scalars.c_str(), (unsigned long long)h);
 }
 
+int64_t n_walk2 = 0, n_cuts = 0;
+
+// ---- the cut of the one-term walk against the kernel's segment formulas -------------------------------------------------
+// (csrc/kernels_walk_impl.h, hrb_walk_kernel: wrows, Jc, j0, j1 as the kernel computes them from P and G for wavefront (seg, col);
+// a wavefront walks steps [j0, j1) iff seg < G.nseg and j0 < j1; edge blocks: workgroups of their own, one block per wavefront,
+// when G.n_edge_wg > 0, else `for (idx = task; idx < P.n_edge; idx += G.ntask)` on every wavefront with task < P.n_edge)
+void check_walk_cut(const qp::WalkPlan& P, const qp::WalkMatrix& M, const qp::WalkKnobs& k, int cu, int reserve, bool row_set, const char* what) {
+  const qp::WalkCut C = qp::walk_cut(P, M, k, cu, reserve, row_set, false);
+  if (!C.taken) {
+    REQUIRE(P.R1 - P.W0 < k.walk_min_blocks || P.R1 - P.W0 < P.S, "%s: a plan of %lld walkable blocks was not taken", what, (long long)(P.R1 - P.W0));
+    return;
+  }
+  ++n_cuts;
+  const qp::WalkGeom& G = C.G;
+#define CUT_REQUIRE(cond) REQUIRE(cond, "%s: walk_cut(cu %d, reserve %d, row set %d, walk_waves %d, walk_dbg %d): " #cond " [L %d nseg %d ntask %d n_walk_wg %d edge_segs %d edge_steps %d n_edge_wg %d ws %d]", \
+                                  what, cu, reserve, (int)row_set, k.walk_waves, k.walk_dbg, G.L, G.nseg, G.ntask, G.n_walk_wg, G.edge_segs, G.edge_steps, G.n_edge_wg, C.ws)
+  CUT_REQUIRE(C.ws == 4 || C.ws == 8);
+  CUT_REQUIRE(G.ntask == G.n_walk_wg * C.ws && (int64_t)G.ntask >= (int64_t)G.nseg * P.S);
+  CUT_REQUIRE(C.grid == (unsigned)(G.n_edge_wg + G.n_walk_wg));
+  CUT_REQUIRE(G.L > G.edge_steps);
+  CUT_REQUIRE(G.edge_segs <= G.nseg);
+  CUT_REQUIRE(G.xlast == M.ncols - 1);
+  const int64_t g = P.g;
+  const int64_t wrows = (P.R1 - P.W0) * (int64_t)kRB;
+  for (int col = 0; col < P.S; ++col) {
+    const int Jc = (int64_t)col * kRB < wrows ? (int)((wrows - (int64_t)col * kRB + g - 1) / g) : 0;
+    int next = 0;   // first step of the column no segment has taken yet
+    for (int seg = 0; seg < G.nseg; ++seg) {
+      const int j0 = seg * G.L - std::min(seg, G.edge_segs) * G.edge_steps;
+      const int j1 = std::min((seg + 1) * G.L - std::min(seg + 1, G.edge_segs) * G.edge_steps, Jc);
+      if (j0 < j1) {
+        CUT_REQUIRE(j0 == next);
+        next = j1;
+      }
+    }
+    CUT_REQUIRE(next == Jc);
+  }
+  if (G.n_edge_wg > 0) {
+    CUT_REQUIRE((int64_t)G.n_edge_wg * C.ws >= P.n_edge);
+    CUT_REQUIRE((int64_t)G.n_edge_wg + G.n_walk_wg <= (int64_t)std::max(cu - reserve, 8) * (8 / C.ws));
+  } else {
+    std::vector<char> reached((size_t)P.n_edge, 0);
+    for (int64_t task = 0; task < G.ntask && task < P.n_edge; ++task)
+      for (int64_t idx = task; idx < P.n_edge; idx += G.ntask) reached[(size_t)idx] = 1;
+    for (int64_t i = 0; i < P.n_edge; ++i) CUT_REQUIRE(reached[(size_t)i]);
+  }
+#undef CUT_REQUIRE
+}
+
+// ---- the cut of the two-term walk (csrc/kernels_walk2_impl.h, hrb_walk2_kernel: zb, ze, Jz, j0 = seg L, j1 = min(j0 + L, Jz) for seg < G.nseg) -----
+void check_walk2_cut(const qp::WalkPlan& P2, const qp::WalkMatrix& M, const qp::WalkKnobs& k, int cu, const char* what) {
+  const qp::Walk2Cut C = qp::walk2_cut(P2, M, k, cu);
+  const qp::Walk2Geom& G = C.G;
+#define CUT_REQUIRE(cond) REQUIRE(cond, "%s: walk2_cut(cu %d, walk_waves %d): " #cond " [W %d S2 %d L %d nseg %d ntask %d n_walk_wg %d]", what, cu, k.walk_waves, G.W, G.S2, G.L, G.nseg, G.ntask, G.n_walk_wg)
+  CUT_REQUIRE(C.taken);
+  ++n_cuts;
+  CUT_REQUIRE(G.W >= 16 && G.W == kRB - 2 * P2.near[P2.nn - 1]);
+  CUT_REQUIRE((int64_t)G.S2 * G.W >= P2.g);
+  const int64_t zb = P2.W0 * (int64_t)kRB, ze = P2.R1 * (int64_t)kRB;
+  const int Jz = (int)((ze - zb + P2.g - 1) / P2.g);
+  CUT_REQUIRE(C.Jz == Jz);
+  int next = 0;
+  for (int seg = 0; seg < G.nseg; ++seg) {
+    const int j0 = seg * G.L, j1 = std::min(j0 + G.L, Jz);
+    CUT_REQUIRE(j0 == next && j0 < j1);
+    next = j1;
+  }
+  CUT_REQUIRE(next == Jz);
+  CUT_REQUIRE(G.ntask == 4 * G.n_walk_wg && (int64_t)G.ntask >= (int64_t)G.nseg * G.S2);
+  CUT_REQUIRE(G.vend == (P2.R1 + (int64_t)P2.K * P2.S) * 64);
+  CUT_REQUIRE(G.xlast == M.ncols - 1);
+#undef CUT_REQUIRE
+}
+
+// every chip size and knob setting the launchers can meet, for one operator's plans (walk_min_blocks lowered: small plans are taken)
+void check_walk_geometry(const qp_operator* op, const char* what) {
+  const qp::WalkMatrix M = qp::walk_matrix(op->A);
+  for (int cu : {8, 64, 256})
+    for (int waves : {0, 64, 1856, 2048}) {
+      qp::WalkKnobs k;
+      k.walk_waves = waves;
+      k.walk_min_blocks = 1;
+      for (int dbg : {0, 1, 4})
+        for (int reserve : {0, 8})
+          for (int row_set = 0; row_set < 2; ++row_set) {
+            k.walk_dbg = dbg;
+            check_walk_cut(op->walk, M, k, cu, reserve, row_set != 0, what);
+          }
+      k.walk_dbg = 0;
+      if (op->walk2.valid) check_walk2_cut(op->walk2, M, k, cu, what);
+    }
+  if (op->walk2.valid) ++n_walk2;
+}
+
+// the named inputs of tests/walk_geometry_cases.h: the same numbers as the launchers computed before the cut became a unit of its own
+void check_cut_table() {
+  int n_one = 0, n_two = 0;
+  for (const CutCase& c : kCutCases) {
+    qp::WalkPlan P;
+    P.valid = 1;
+    P.nn = c.p.nn, P.K = c.p.K, P.z0 = c.p.z0, P.S = c.p.S, P.xl = c.p.xl, P.fd = c.p.fd, P.g = c.p.g;
+    for (int i = 0; i < 4; ++i) P.near[i] = c.p.near[i];
+    P.R0 = c.p.R0, P.R1 = c.p.R1, P.W0 = c.p.W0, P.n_edge = c.p.n_edge;
+    const qp::WalkMatrix M{c.m.nblocks, c.m.nrows, c.m.ncols, c.m.real != 0};
+    const qp::WalkKnobs k{c.k.walk_waves, c.k.walk_nt, c.k.walk_dbg, c.k.walk_min_blocks, -1};
+    if (!c.two) {
+      ++n_one;
+      const qp::WalkCut C = qp::walk_cut(P, M, k, c.cu, c.reserve_cu, c.row_set != 0, c.no_edges != 0);
+      const qp::WalkGeom& G = C.G;
+      REQUIRE((int)C.taken == c.taken, "cut table, %s: taken %d", c.name, (int)C.taken);
+      if (!C.taken) continue;
+      REQUIRE(C.ws == c.ws && C.ntm == c.ntm && C.grid == c.grid, "cut table, %s: ws %d ntm %d grid %u", c.name, C.ws, C.ntm, C.grid);
+      REQUIRE(G.L == c.g1.L && G.nseg == c.g1.nseg && G.n_walk_wg == c.g1.n_walk_wg && G.ntask == c.g1.ntask && G.edge_segs == c.g1.edge_segs &&
+                  G.edge_steps == c.g1.edge_steps && G.edge_last == c.g1.edge_last && G.xlast == c.g1.xlast && G.n_edge_wg == c.g1.n_edge_wg,
+              "cut table, %s: L %d nseg %d n_walk_wg %d ntask %d edge_segs %d edge_steps %d edge_last %d xlast %lld n_edge_wg %d", c.name, G.L, G.nseg,
+              G.n_walk_wg, G.ntask, G.edge_segs, G.edge_steps, G.edge_last, (long long)G.xlast, G.n_edge_wg);
+    } else {
+      ++n_two;
+      const qp::Walk2Cut C = qp::walk2_cut(P, M, k, c.cu);
+      const qp::Walk2Geom& G = C.G;
+      REQUIRE((int)C.taken == c.taken && C.ntm == c.ntm, "cut table, %s: taken %d ntm %d", c.name, (int)C.taken, C.ntm);
+      REQUIRE(G.L == c.g2.L && G.nseg == c.g2.nseg && G.ntask == c.g2.ntask && G.n_walk_wg == c.g2.n_walk_wg && (unsigned)G.n_walk_wg == c.grid && G.S2 == c.g2.S2 &&
+                  G.W == c.g2.W && G.xlast == c.g2.xlast && G.vend == c.g2.vend,
+              "cut table, %s: L %d nseg %d ntask %d n_walk_wg %d S2 %d W %d xlast %lld vend %lld", c.name, G.L, G.nseg, G.ntask, G.n_walk_wg, G.S2, G.W,
+              (long long)G.xlast, (long long)G.vend);
+      qp::WalkPlan P1 = P;   // the operator's one-term plan
+      P1.W0 = P.W0 - (int64_t)P.K * P.S;
+      P1.R1 = P.R1 + (int64_t)P.K * P.S;
+      REQUIRE((int)qp::walk2_wanted(P1, P, M, k, c.cu) == c.wanted, "cut table, %s: wanted != %d", c.name, c.wanted);
+    }
+  }
+  // the table's own numbers against the figures the sources document (head of tests/walk_geometry_cases.h)
+  const CutCase* t = kCutCases;
+  REQUIRE(t[0].g1.ntask <= 768 && t[0].ws == 4 && t[1].g1.ntask == 1024, "cut table: 768 / 1024 wavefronts inside the cache");
+  REQUIRE(t[2].g1.n_edge_wg == 24 && t[2].ws == 8 && t[2].g1.ntask <= 8 * (256 - 24) && t[2].grid <= 256, "cut table: 8 x (256 - 24) = 1856 beyond the cache");
+  REQUIRE(t[3].g1.n_edge_wg == 0 && t[3].g1.ntask == 2048, "cut table: 2048 with the edge blocks inside the walk");
+  for (const CutCase& c : kCutCases)
+    if (c.two && c.p.nn == 4 && c.p.g == 1024) REQUIRE(c.g2.W == 56 && c.g2.S2 == 19, "cut table, %s: W = 56, S2 = 19", c.name);
+  REQUIRE(n_one >= 9 && n_two >= 3, "cut table: %d one-term and %d two-term cases", n_one, n_two);
+  std::printf("walk geometry: %d named cases (%d one-term, %d two-term) match the table\n", n_one + n_two, n_one, n_two);
+}
+
 void check_operator(qp_ctx* ctx, const std::vector<Csr>& terms, int ncoeffs, int format, const char* what) {
   std::vector<qp_matrix*> ms;
   for (const Csr& t : terms) {
@@ -279,6 +426,7 @@ void check_operator(qp_ctx* ctx, const std::vector<Csr>& terms, int ncoeffs, int
       for (int64_t i = 0; i < op->walk.n_edge; ++i)
         REQUIRE(op->walk.edge_map[i] >= 0 && op->walk.edge_map[i] < A.nblocks, "%s: edge block %d", what, op->walk.edge_map[i]);
       REQUIRE(op->walk.R0 >= 0 && op->walk.R1 <= A.nblocks && op->walk.W0 >= op->walk.R0, "%s: walk run [%lld, %lld)", what, (long long)op->walk.R0, (long long)op->walk.R1);
+      check_walk_geometry(op, what);
     }
     if (op->cv.valid) {     // value dictionary: every code inside its block's table
       for (int64_t b = 0; b < A.nblocks; ++b) {
@@ -511,6 +659,9 @@ int main(int argc, char** argv) {
     std::vector<Csr> terms{random_csr(rng, nr, nc, 12, 100000, false)};
     check_operator(ctx, terms, 0, rep % 3 == 0 ? QP_FMT_CSR : QP_FMT_RBCSR, "forced column-blocked mirror");
   }
+  check_cut_table();
+  std::printf("walk geometry: %lld cuts of %lld one-term and %lld two-term plans keep every strip step in exactly one segment\n", (long long)n_cuts,
+              (long long)n_walked, (long long)n_walk2);
   qp_ctx_destroy(ctx);
   std::printf("sanitizer run clean: %lld operators (%lld Hermitian-packed, %lld with a strip-walk plan, %lld with a value dictionary, %lld with a "
               "column-blocked mirror, %lld dense)\n",

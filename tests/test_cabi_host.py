@@ -451,19 +451,23 @@ def test_host_index_work_under_sanitizers(tmp_path):
     bounds-checked) and fuzzed over tall / wide / 1-row / N < 64 / empty-row shapes, lattices and spin chains
     (tests/sanitize_host_index.cpp; the 5681 x 358 operator of the round-4 GPU memory fault is the first case).  Every stored slot
     -- pads and the lanes beyond the last row included -- must decode to a column inside the matrix, every pad must be zero.
-    The layout unit (csrc/operator_layout.cpp) must stay pure host code: it compiles without the HIP stand-in on the include path."""
+    The layout unit (csrc/operator_layout.cpp) and the launch geometry of the strip walks (csrc/walk_geometry.cpp) must stay pure host
+    code: they compile without the HIP stand-in on the include path.  For every operator with a strip-walk plan the harness sweeps the
+    cut of its launches over chip sizes and knobs against the kernels' own segment formulas (every strip step in exactly one
+    segment, every edge block reached, the launch fits the chip) and checks a table of named inputs (tests/walk_geometry_cases.h)."""
     import shutil
     import subprocess
     if shutil.which("g++") is None:
         pytest.skip("g++ not available")
     csrc = os.path.join(ROOT, "quantumpropagators.jl_amd", "csrc")
     exe = str(tmp_path / "host_index_san")
-    pure = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", csrc, os.path.join(csrc, "operator_layout.cpp")], capture_output=True, text=True)
-    assert pure.returncode == 0, pure.stderr[-3000:]
+    for unit in ("operator_layout.cpp", "walk_geometry.cpp"):
+        pure = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", csrc, os.path.join(csrc, unit)], capture_output=True, text=True)
+        assert pure.returncode == 0, pure.stderr[-3000:]
     build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-x", "c++",
                             "-I", os.path.join(ROOT, "tests", "hip_host_shim"), "-I", csrc,
                             os.path.join(ROOT, "tests", "sanitize_host_index.cpp"), os.path.join(csrc, "host_numerics.cpp"),
-                            os.path.join(csrc, "operator_layout.cpp"),
+                            os.path.join(csrc, "operator_layout.cpp"), os.path.join(csrc, "walk_geometry.cpp"),
                             "-o", exe, "-lpthread"], capture_output=True, text=True)
     if build.returncode != 0 and "sanitize" in build.stderr and "cannot find" in build.stderr:
         pytest.skip("sanitizer runtime not installed")
@@ -475,3 +479,7 @@ def test_host_index_work_under_sanitizers(tmp_path):
     assert "sanitizer run clean" in run.stdout
     n = {k: int(v) for v, k in __import__("re").findall(r"(\d+) (operators|Hermitian-packed|with a strip-walk plan|with a value dictionary|with a column-blocked mirror)", run.stdout)}
     assert n["operators"] > 300 and n["with a strip-walk plan"] > 20 and n["with a value dictionary"] > 20 and n["with a column-blocked mirror"] >= 4
+    geo = __import__("re").search(r"walk geometry: (\d+) cuts of (\d+) one-term and (\d+) two-term plans", run.stdout)
+    assert geo and int(geo.group(2)) == n["with a strip-walk plan"] and int(geo.group(3)) >= 1 and int(geo.group(1)) >= 100 * int(geo.group(2))
+    cases = __import__("re").search(r"walk geometry: (\d+) named cases .* match the table", run.stdout)
+    assert cases and int(cases.group(1)) >= 12
