@@ -454,6 +454,11 @@ inline bool mgs_lowsync_fits(int j) { return sizeof(double2) * (size_t)(3 * (j +
 // w *= 1/sqrt(sum part_in.x);  hess_slot = dt * norm
 int launch_norm_scale(hipStream_t s, double2* w, const double2* part_in, double2* hess_slot, double dt,
                       int64_t n, Stats* st);
+// h = sqrt(sum part_in.x);  hess_slot = dt * h, norm_slot = h;  w = w_in / h, or w_in as it is when h < norm_min (w_in may be w);
+// flag != NULL: flag_value is stored there, visible to the host, once the two slots are written
+int launch_norm_guard_scale(hipStream_t s, double2* w, const double2* w_in, const double2* part_in, double2* hess_slot,
+                            double* norm_slot, double dt, double norm_min, int64_t n, unsigned* flag, unsigned flag_value,
+                            Stats* st);
 bool launch_combine2_vecs(hipStream_t s, double2* out1, int use_out1, int m1, const double2* coefs1, double2* out2, int m2,
                           const double2* coefs2, const double2* Q, int64_t ldq, double2* norm_partials, int64_t n,
                           Stats* st);

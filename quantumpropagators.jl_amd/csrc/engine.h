@@ -266,6 +266,12 @@ inline void dev_release(T*& p) {
   if (p) (void)hipFree((void*)p);
   p = nullptr;
 }
+// the same for a pinned host array
+template <class T>
+inline void host_release(T*& p) {
+  if (p) (void)hipHostFree((void*)p);
+  p = nullptr;
+}
 
 // sum kRedBlocks partials on the host in index order
 inline cplx sum_partials(const double2* h) {

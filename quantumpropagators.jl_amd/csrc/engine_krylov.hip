@@ -1,5 +1,6 @@
 // arnoldi!, newton!, ritzvals / specrange and the building blocks of their row-partitioned
 // variants.
+#include <functional>
 #include <thread>
 
 #include "engine.h"
@@ -12,8 +13,6 @@
 #else
 #define QP_CPU_RELAX() std::this_thread::yield()
 #endif
-
-#include <functional>
 
 extern "C" {
 
@@ -61,27 +60,27 @@ int qp_krylov_destroy(qp_krylov* q) {
   if (!q) return QP_OK;
   (void)hipSetDevice(q->ctx->device);
   (void)hipStreamSynchronize(q->ctx->stream);
-  if (q->Q) (void)hipFree(q->Q);
-  if (q->raw[0]) (void)hipFree(q->raw[0]);
-  if (q->raw[1]) (void)hipFree(q->raw[1]);
-  if (q->hess_dev) (void)hipFree(q->hess_dev);
-  if (q->norms_dev) (void)hipFree(q->norms_dev);
-  if (q->part) (void)hipFree(q->part);
-  if (q->md_part) (void)hipFree(q->md_part);
-  if (q->gram) (void)hipFree(q->gram);
-  if (q->h_hess) (void)hipHostFree(q->h_hess);
-  if (q->h_norms) (void)hipHostFree(q->h_norms);
-  if (q->col_flags) (void)hipHostFree(q->col_flags);
-  if (q->hcoef) (void)hipFree(q->hcoef);
-  if (q->mgs_coef) (void)hipFree(q->mgs_coef);
-  if (q->ticket) (void)hipFree(q->ticket);
-  if (q->op_gram) (void)hipFree(q->op_gram);
-  if (q->op_hhat) (void)hipFree(q->op_hhat);
-  if (q->op_part[0]) (void)hipFree(q->op_part[0]);
-  if (q->op_part[1]) (void)hipFree(q->op_part[1]);
-  if (q->op_svals) (void)hipFree(q->op_svals);
-  if (q->op_nu_dev) (void)hipFree(q->op_nu_dev);
-  if (q->h_nu) (void)hipHostFree(q->h_nu);
+  dev_release(q->Q);
+  dev_release(q->raw[0]);
+  dev_release(q->raw[1]);
+  dev_release(q->hess_dev);
+  dev_release(q->norms_dev);
+  dev_release(q->part);
+  dev_release(q->md_part);
+  dev_release(q->gram);
+  dev_release(q->hcoef);
+  dev_release(q->mgs_coef);
+  dev_release(q->ticket);
+  dev_release(q->op_gram);
+  dev_release(q->op_hhat);
+  dev_release(q->op_part[0]);
+  dev_release(q->op_part[1]);
+  dev_release(q->op_svals);
+  dev_release(q->op_nu_dev);
+  host_release(q->h_hess);
+  host_release(q->h_norms);
+  host_release(q->col_flags);
+  host_release(q->h_nu);
   for (hipEvent_t e : q->col_events) (void)hipEventDestroy(e);
   delete q;
   return QP_OK;
@@ -97,6 +96,8 @@ int qp_krylov_download(const qp_krylov* q, int i, qp_c128* host) {
   return QP_OK;
   QP_CATCH
 }
+
+}  // extern "C"
 
 namespace {
 
@@ -171,53 +172,265 @@ int arnoldi_column(qp_operator* op, qp_krylov* q, int j, double dt, double2* hco
   return QP_OK;
 }
 
-}  // namespace
-
-__global__ void norm_guard_scale_kernel(double2* w, const double2* __restrict__ part_in, double2* hess_slot,
-                                        double* norm_slot, double dt, double norm_min, int64_t n, const double2* w_in,
-                                        unsigned* flag, unsigned flag_value);
-
-// workgroups of norm_guard_scale_kernel: every one re-reduces the 256 partials, so no more of them than
-// two elements per lane need (the partial order, hence the norm, does not depend on the grid)
-static inline int guard_grid(int64_t n) {
-  return (int)std::max<int64_t>(64, std::min<int64_t>(2048, (n + 2 * qp::kThreads - 1) / (2 * qp::kThreads)));
+// the two scratch vectors between which the unnormalised vectors of a folded or one-pass sweep ping-pong, on first use
+int ensure_raw(qp_krylov* q) {
+  if (q->raw[0]) return QP_OK;
+  QP_CHECK(dev_alloc(&q->raw[0], (size_t)q->n));
+  QP_CHECK(dev_alloc(&q->raw[1], (size_t)q->n));
+  return QP_OK;
 }
+
+// the one-pass sweep's buffers (qp_krylov in engine.h says what they hold), on first use
+int ensure_onepass(qp_krylov* q) {
+  if (q->op_gram) return QP_OK;
+  const int ldd = q->nvec;
+  QP_CHECK(dev_alloc(&q->op_gram, (size_t)ldd * ldd));
+  QP_CHECK(dev_alloc(&q->op_hhat, (size_t)ldd * ldd));
+  QP_CHECK(dev_alloc(&q->op_part[0], (size_t)qp::op_part_slots(ldd) * kRedBlocks));
+  QP_CHECK(dev_alloc(&q->op_part[1], (size_t)qp::op_part_slots(ldd) * kRedBlocks));
+  QP_CHECK(dev_alloc(&q->op_svals, (size_t)ldd + 1));
+  QP_CHECK(dev_alloc(&q->op_nu_dev, (size_t)ldd + 1));
+  QP_HIP(hipHostMalloc((void**)&q->h_nu, sizeof(double) * (size_t)(ldd + 1), hipHostMallocMapped));
+  QP_HIP(hipHostGetDevicePointer((void**)&q->nu_map, q->h_nu, 0));
+  return QP_OK;
+}
+
+// Spin until the device has stored `seq` into *flag (coherent pinned memory): the ONE place where the host polls what a running
+// kernel writes.  Never for good.  A flag that must come (`seen` null) is given timeout_s by the clock (looked at every 2^20
+// polls); then the host falls back to the stream, looks once more, and fails if "`what` j" still has not announced itself.
+// A flag that only lets the host start early (`seen` given) is given max_spins polls; running out of them is no error:
+// *seen says whether the flag came, and the stream is left alone.
+int wait_flag(qp_ctx* ctx, const unsigned* flag, unsigned seq, double timeout_s, const char* what, int j, bool* seen = nullptr,
+              unsigned max_spins = 0) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  for (unsigned spins = 1;; ++spins) {
+    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) {
+      if (seen) *seen = true;
+      return QP_OK;
+    }
+    if (seen ? spins >= max_spins
+             : (spins & 0xfffffu) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count() > timeout_s)
+      break;
+    QP_CPU_RELAX();
+  }
+  if (!seen) QP_HIP(hipStreamSynchronize(ctx->stream));
+  const bool there = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq;
+  if (seen) *seen = there;
+  return there || seen ? QP_OK : qp::fail(QP_E_INTERNAL, "%s %d never announced itself to the host", what, j);
+}
+
+}  // namespace
 
 // arnoldi! with an optional normalisation of the start vector: beta_out != NULL means `psi` is
 // not normalised; q_0 = psi / |psi| and *beta_out = |psi| (newton! :268-272 folded in, so that
 // the persistent small-system kernel does it in the same launch).
 //
-// on_column != NULL (multi-launch path only): the sweep is enqueued whole, every column followed by
-// an event; the host then takes the columns as they arrive and calls on_column(j) once column j is
+// on_column != NULL: the host takes the columns as they arrive and calls on_column(j) once column j is
 // in Hess -- the caller's work on the leading (j+1) x (j+1) block (newton!: its eigenvalues,
-// src/newton.jl:297) overlaps the device's work on the later columns.
+// src/newton.jl:297) overlaps the device's work on the later columns.  (Not on the persistent small sweep,
+// whose columns arrive together: its caller goes through them afterwards.)
 using ColumnHook = std::function<int(int)>;
 constexpr double kOnepassNormDrift = 1e-4;   // |nu_i - 1| of a one-pass sweep's stored basis vectors beyond which the sweep is redone
+constexpr double kColumnTimeout = 5.0;       // seconds the host polls for a column's flag before it falls back to the stream
+
+namespace {
+
+// What the host needs to know of an enqueued sweep to take its columns (collect_columns)
+enum class Announce {
+  stream_end,   // nobody waits for single columns: the sweep is complete when the stream is
+  event,        // column j records col_events[j]
+  flag,         // the kernel after column j stores the sweep's sequence number into col_flags[j]
+};
+struct SweepShape {
+  Announce announce = Announce::stream_end;
+  bool extended = false;     // m + 1 basis vectors, m + 1 rows of Hess: the last column has a norm and a kernel after it
+  bool early_last = false;   // the last column also raises its early flag, once its coefficients (not yet its norm) are written
+};
+
+// The columns of an enqueued sweep, as they arrive in the pinned buffers: wait for column j, copy its rows into Hess, run the hook
+// (for the last column already on its early flag, where armed: that hook is the one the device waits for, and its Hessenberg
+// block does not contain the column's norm), stop at a breakdown (src/arnoldi.jl:91-95); then leave the stream drained unless the
+// sweep announced itself to the end.  *m_out = number of columns kept.  A failed hook ends the sweep with the hook's status.
+int collect_columns(qp_krylov* q, int m, const SweepShape& sw, double norm_min, qp_c128* Hess, int ldh, const ColumnHook* on_column,
+                    int* m_out) {
+  qp_ctx* ctx = q->ctx;
+  const int ldd = q->nvec, dim = sw.extended ? m + 1 : m;
+  const cplx* hh = reinterpret_cast<const cplx*>(q->h_hess);
+  const double* hn = q->h_norms;
+  auto copy_column = [&](int j, int rows) {
+    for (int i = 0; i < rows; ++i) {
+      const cplx v = hh[(size_t)j * ldd + i];
+      Hess[(size_t)j * ldh + i] = qp_c128{v.real(), v.imag()};
+    }
+  };
+  if (sw.announce == Announce::stream_end) QP_HIP(hipStreamSynchronize(ctx->stream));
+  int m_eff = m, hook_rc = QP_OK;
+  for (int j = 0; j < m; ++j) {
+    const bool last = j + 1 == m;
+    bool hooked = false;
+    if (sw.early_last && last && on_column) {   // coefficients first, hook, then the norm
+      bool early = false;
+      QP_CHECK(wait_flag(ctx, q->col_flags + q->nvec + j, q->seq, 0.0, nullptr, j, &early, 1u << 24));
+      if (early) {
+        copy_column(j, j + 1);
+        if ((hook_rc = (*on_column)(j)) != QP_OK) break;
+        hooked = true;
+      }
+    }
+    if (sw.announce == Announce::event) {
+      QP_HIP(hipEventSynchronize(q->col_events[j]));
+    } else if (sw.announce == Announce::flag) {
+      if (last && !sw.extended)   // no kernel after the last column that could announce it
+        QP_HIP(hipStreamSynchronize(ctx->stream));
+      else
+        QP_CHECK(wait_flag(ctx, q->col_flags + j, q->seq, kColumnTimeout, "Arnoldi column", j));
+    }
+    if (last) q->t_last_column = std::chrono::steady_clock::now();
+    copy_column(j, std::min(j + 2, dim));
+    if (on_column && !hooked && (hook_rc = (*on_column)(j)) != QP_OK) break;
+    if ((!last || sw.extended) && hn[j] < norm_min) {   // dimensionality exhausted  :91-95
+      m_eff = j + 1;
+      break;
+    }
+  }
+  // the columns after a breakdown or a failed hook are discarded: wait for them.  (A complete extended sweep of flags needs no wait:
+  // its last column announced itself, and what the device still does -- normalising the last vector -- is consumed in stream order.)
+  const bool announced_to_the_end = sw.announce == Announce::flag && sw.extended && m_eff == m && hook_rc == QP_OK;
+  if (sw.announce != Announce::stream_end && !announced_to_the_end) QP_HIP(hipStreamSynchronize(ctx->stream));
+  if (hook_rc != QP_OK) return hook_rc;
+  *m_out = m_eff;
+  return QP_OK;
+}
+
+// ---- the three ways to enqueue a sweep ----
+
+// does the persistent small-system kernel take this operator, and with which plan?
+bool small_sweep_fits(const qp_operator* op, const qp_krylov* q, int m, qp::SmallArgs* plan) {
+  const qp_ctx* ctx = op->ctx;
+  if (!(ctx->tun.small_nnz > 0 && op->A.nnz <= (int64_t)ctx->tun.small_nnz * (qp::kSmallEptArnoldi / qp::kSmallEpt) &&
+        qp::small_arnoldi_fits(q->n, m)))
+    return false;
+  int64_t maxrow = 0;
+  for (int64_t r = 0; r < q->n; ++r) maxrow = std::max<int64_t>(maxrow, op->u_rowptr[r + 1] - op->u_rowptr[r]);
+  // the plan of the 16-slot kernels where it exists (same lanes per row, hence the same rounding, as
+  // before the 32-slot variants were added), the larger one only for systems that need it
+  return qp::small_plan(q->n, maxrow, plan, qp::kSmallEpt) || qp::small_plan(q->n, maxrow, plan, qp::kSmallEptArnoldi);
+}
+
+// all m columns in one persistent single-workgroup launch (kernels_small.hip: arnoldi_small_kernel), then one download of the
+// Hessenberg matrix and the norms into pinned memory; |psi| (normalize_start) arrives in norms slot ldd - 1, which is never a column's
+int enqueue_small_sweep(qp_operator* op, qp_krylov* q, const qp::SmallArgs& plan, int m, const qp_state* psi, double dt, int extended,
+                        double norm_min, bool normalize_start) {
+  qp_ctx* ctx = op->ctx;
+  const int ldd = q->nvec;
+  QP_CHECK(operator_csr_mirror(op, false));
+  qp::SmallArnoldiArgs a;
+  a.n = q->n;
+  a.lanes = plan.lanes;
+  a.ent = plan.ent;
+  a.rows_per_group = plan.rows_per_group;
+  a.rowptr = op->m_rowptr;
+  a.cols = op->m_cols;
+  a.map = op->m_map;
+  a.vals = op->A.vals;
+  a.start = psi->d;
+  a.Q = q->Q;
+  a.hess = q->hess_dev;
+  a.norms = q->norms_dev;
+  a.ldd = ldd;
+  a.m = m;
+  a.extended = extended;
+  a.dt = dt;
+  a.norm_min = norm_min;
+  a.normalize_start = normalize_start ? 1 : 0;     // the kernel also zero-fills hess / norms
+  QP_CHECK(qp::launch_arnoldi_small(ctx->stream, a, &ctx->stats));
+  q->gram_rows = 0;
+  QP_HIP(hipMemcpyAsync(q->h_hess, q->hess_dev, (size_t)ldd * ldd * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+  QP_HIP(hipMemcpyAsync(q->h_norms, q->norms_dev, (size_t)ldd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  return QP_OK;
+}
+
+// Hessenberg entries and norms of the multi-launch and the one-pass sweep go straight into the pinned host buffers (nothing of
+// an earlier sweep is in flight: every sweep ends with a synchronisation)
+void clear_pinned_columns(qp_krylov* q) {
+  std::memset(q->h_hess, 0, sizeof(double2) * (size_t)q->nvec * q->nvec);
+  std::memset(q->h_norms, 0, sizeof(double) * (size_t)q->nvec);
+}
+void next_sequence_number(qp_krylov* q) { q->seq = q->seq + 1 == 0 ? 1 : q->seq + 1; }   // (0 is what the flags start with)
+
+// The multi-launch sweep: mat-vec + projection per column.  Folded (stored operators, m > 1): "norm + scale" of column j is done by
+// the mat-vec of column j + 1 (it scales its row sums by 1 / |q_j| and stores the normalised q_j as it goes; src/arnoldi.jl:89-96
+// applied on the fly), and the unnormalised vectors ping-pong between two scratch vectors; plain: a norm kernel after every column.
+// await_columns: the host will take the columns one by one -- a folded sweep then announces them through col_flags (the sweep gets a
+// new sequence number), a plain one through events.  *sw says what was enqueued.
+int enqueue_multilaunch_sweep(qp_operator* op, qp_krylov* q, int m, const qp_state* psi, double dt, bool extended, double norm_min,
+                              double* beta_out, bool await_columns, SweepShape* sw) {
+  qp_ctx* ctx = op->ctx;
+  const int ldd = q->nvec;
+  clear_pinned_columns(q);
+  QP_HIP(hipMemsetAsync(q->ticket, 0, sizeof(unsigned), ctx->stream));
+  QP_HIP(hipMemcpyAsync(q->q(0), psi->d, (size_t)q->n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));  // :79
+  if (beta_out) {
+    cplx n2;
+    QP_CHECK(dot_sync(ctx, q->q(0), q->q(0), q->n, &n2));
+    *beta_out = std::sqrt(n2.real());
+    QP_CHECK(qp::launch_scal(ctx->stream, q->q(0), make_double2(1.0 / *beta_out, 0.0), q->n, &ctx->stats));
+  }
+  const bool fold = op->A.format != QP_FMT_MATFREE && m > 1;
+  const bool flags = fold && await_columns;
+  sw->announce = !await_columns ? Announce::stream_end : fold ? Announce::flag : Announce::event;
+  sw->extended = extended;
+  sw->early_last = false;
+  if (fold) QP_CHECK(ensure_raw(q));
+  if (flags) next_sequence_number(q);
+  while (await_columns && (int)q->col_events.size() < m) {
+    hipEvent_t e;
+    QP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    q->col_events.push_back(e);
+  }
+  for (int j = 0; j < m; ++j) {
+    const bool last = j + 1 == m;
+    double2* hcol = q->hess_map + (size_t)j * ldd;
+    double2* w = fold ? q->raw[(j + 1) & 1] : q->q(j + 1);   // where the column leaves its (unnormalised) new vector
+    if (fold) {
+      FoldArgs fa{q->part + (size_t)(j & 1) * kRedBlocks, j > 0 ? q->hess_map + (size_t)(j - 1) * ldd + j : nullptr,
+                  j > 0 ? q->norms_map + (j - 1) : nullptr, norm_min, (flags && j > 0) ? q->col_flags_map + (j - 1) : nullptr,
+                  q->seq};
+      // The hook of the LAST column is the one the device waits for (the others run while it works on later columns):
+      // its Hessenberg block does not contain the column's norm, so it may start as soon as the projection kernel has
+      // solved for the coefficients -- while that kernel still streams the basis.
+      if (flags && last && j > 0) {
+        fa.early_flag = q->col_flags_map + q->nvec + j;
+        fa.early_armed = &sw->early_last;
+      }
+      QP_CHECK(arnoldi_column(op, q, j, dt, hcol, j == 0 ? q->q(0) : q->raw[j & 1], w, j > 0 ? &fa : nullptr));
+    } else {
+      QP_CHECK(arnoldi_column(op, q, j, dt, hcol));
+    }
+    // norm + guarded scale of the new vector into the basis (:88-97).  A folded sweep leaves that to the next column's mat-vec: only
+    // its last vector remains -- normalised here (extended), where the kernel also announces the last column, or handed over as it is
+    if (fold ? (last && extended) : (!last || extended)) {
+      QP_CHECK(qp::launch_norm_guard_scale(ctx->stream, q->q(j + 1), w, q->part + (size_t)((j + 1) & 1) * kRedBlocks, hcol + (j + 1),
+                                           q->norms_map + j, dt, norm_min, q->n, flags ? q->col_flags_map + j : nullptr, q->seq,
+                                           &ctx->stats));
+    } else if (fold) {
+      QP_HIP(hipMemcpyAsync(q->q(j + 1), w, (size_t)q->n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if (sw->announce == Announce::event) QP_HIP(hipEventRecord(q->col_events[j], ctx->stream));
+  }
+  return QP_OK;
+}
 
 // The sweep that reads the basis once per column (knob arnoldi_onepass; kernels_onepass.hip says how): m + 1 column kernels, a
 // single-workgroup solve after each; column j of the Hessenberg matrix reaches the pinned host buffer with the solve after
 // column kernel j + 1 and announces itself through col_flags[j], like the folded sweep's.  The stored basis vectors have norm
 // q->h_nu[i] (1 to rounding unless a projection cancelled nearly everything): the caller divides its combination coefficients by it.
-static int arnoldi_onepass(qp_operator* op, qp_krylov* q, int m, const qp_state* psi, double dt, double norm_min, qp_c128* Hess,
-                           int ldh, int* m_out, double* beta_out, const ColumnHook* on_column) {
+int enqueue_onepass_sweep(qp_operator* op, qp_krylov* q, int m, const qp_state* psi, double dt, double* beta_out) {
   qp_ctx* ctx = op->ctx;
   const int ldd = q->nvec;
-  if (!q->op_gram) {
-    QP_CHECK(dev_alloc(&q->op_gram, (size_t)ldd * ldd));
-    QP_CHECK(dev_alloc(&q->op_hhat, (size_t)ldd * ldd));
-    QP_CHECK(dev_alloc(&q->op_part[0], (size_t)qp::op_part_slots(ldd) * kRedBlocks));
-    QP_CHECK(dev_alloc(&q->op_part[1], (size_t)qp::op_part_slots(ldd) * kRedBlocks));
-    QP_CHECK(dev_alloc(&q->op_svals, (size_t)ldd + 1));
-    QP_CHECK(dev_alloc(&q->op_nu_dev, (size_t)ldd + 1));
-    QP_HIP(hipHostMalloc((void**)&q->h_nu, sizeof(double) * (size_t)(ldd + 1), hipHostMallocMapped));
-    QP_HIP(hipHostGetDevicePointer((void**)&q->nu_map, q->h_nu, 0));
-  }
-  if (!q->raw[0]) {
-    QP_CHECK(dev_alloc(&q->raw[0], (size_t)q->n));
-    QP_CHECK(dev_alloc(&q->raw[1], (size_t)q->n));
-  }
-  std::memset(q->h_hess, 0, sizeof(double2) * (size_t)ldd * ldd);
-  std::memset(q->h_norms, 0, sizeof(double) * (size_t)ldd);
+  QP_CHECK(ensure_onepass(q));
+  QP_CHECK(ensure_raw(q));
+  clear_pinned_columns(q);
   for (int i = 0; i <= ldd; ++i) q->h_nu[i] = 1.0;
   double s0 = 1.0;
   if (beta_out) {   // newton! :268-272: beta = |Psi|, q_0 = Psi / beta -- the first column kernel scales by 1 / beta
@@ -226,53 +439,57 @@ static int arnoldi_onepass(qp_operator* op, qp_krylov* q, int m, const qp_state*
     *beta_out = std::sqrt(n2.real());
     s0 = 1.0 / *beta_out;
   }
-  q->seq = q->seq + 1 == 0 ? 1 : q->seq + 1;
+  next_sequence_number(q);
   q->gram_rows = 0;            // (the low-synchronisation sweep's Gram rows do not describe this basis)
   q->nu_valid = true;
-  {
-    const qp::ScopedRange mv_range(ctx->tun.roctx != 0 || qp::ranges_enabled_by_env(), "matrix-vector product");
-    QP_CHECK(qp::launch_arnoldi_onepass_sweep(ctx->stream, op->A, psi->d, s0, q->Q, q->n, q->raw, m, ldd, q->op_part, q->op_gram,
-                                              q->op_hhat, q->op_svals, q->op_nu_dev, dt, q->hess_map, q->norms_map, q->nu_map,
-                                              q->col_flags_map, q->seq, &ctx->stats));
-  }
-  const cplx* hh = reinterpret_cast<const cplx*>(q->h_hess);
-  const double* hn = q->h_norms;
-  int m_eff = m, hook_rc = QP_OK;
-  for (int j = 0; j < m; ++j) {
-    const auto t_begin = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (__atomic_load_n(&q->col_flags[j], __ATOMIC_ACQUIRE) != q->seq) {
-      QP_CPU_RELAX();
-      if ((++spins & 0xfffffu) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count() > 5.0) {
-        QP_HIP(hipStreamSynchronize(ctx->stream));      // never spin for good: fall back to the stream and look once more
-        if (__atomic_load_n(&q->col_flags[j], __ATOMIC_ACQUIRE) != q->seq)
-          return qp::fail(QP_E_INTERNAL, "Arnoldi column %d never announced itself to the host", j);
-      }
-    }
-    if (j + 1 == m) q->t_last_column = std::chrono::steady_clock::now();
-    for (int i = 0; i < std::min(j + 2, m + 1); ++i) {
-      const cplx v = hh[(size_t)j * ldd + i];
-      Hess[(size_t)j * ldh + i] = qp_c128{v.real(), v.imag()};
-    }
-    if (on_column && (hook_rc = (*on_column)(j)) != QP_OK) break;
-    if (hn[j] < norm_min) {      // dimensionality exhausted  src/arnoldi.jl:91-95
-      m_eff = j + 1;
-      break;
-    }
-  }
-  // a complete sweep needs no wait (its last column announced itself; the stream is consumed in order); after a breakdown or
-  // a failed hook the later columns are discarded: wait for them
-  if (m_eff != m || hook_rc != QP_OK) QP_HIP(hipStreamSynchronize(ctx->stream));
-  if (hook_rc != QP_OK) return hook_rc;
-  if (m_eff < m) {
+  const qp::ScopedRange mv_range(ctx->tun.roctx != 0 || qp::ranges_enabled_by_env(), "matrix-vector product");
+  return qp::launch_arnoldi_onepass_sweep(ctx->stream, op->A, psi->d, s0, q->Q, q->n, q->raw, m, ldd, q->op_part, q->op_gram,
+                                          q->op_hhat, q->op_svals, q->op_nu_dev, dt, q->hess_map, q->norms_map, q->nu_map,
+                                          q->col_flags_map, q->seq, &ctx->stats);
+}
+
+// A whole one-pass sweep: always extended, its columns always awaited by flag (hook or not), no early flag.
+int onepass_sweep(qp_operator* op, qp_krylov* q, int m, const qp_state* psi, double dt, double norm_min, qp_c128* Hess, int ldh,
+                  int* m_out, double* beta_out, const ColumnHook* on_column) {
+  QP_CHECK(enqueue_onepass_sweep(op, q, m, psi, dt, beta_out));
+  QP_CHECK(collect_columns(q, m, SweepShape{Announce::flag, true, false}, norm_min, Hess, ldh, on_column, m_out));
+  if (*m_out < m) {
     // the reference leaves the vector of a breakdown UNNORMALISED (src/arnoldi.jl:91-95 breaks before :96); the stored one was
     // scaled by s: its coefficient is to be divided by nu / h instead of nu
-    const double h = hn[m_eff - 1];
-    q->h_nu[m_eff] = h > 0.0 ? q->h_nu[m_eff] / h : 0.0;
+    const double h = q->h_norms[*m_out - 1];
+    q->h_nu[*m_out] = h > 0.0 ? q->h_nu[*m_out] / h : 0.0;
   }
-  *m_out = m_eff;
   return QP_OK;
 }
+
+// The one-pass sweep never applies H to the new basis vector itself: it carries a_{t+1} = s (H a_t - sum gamma_i q_i) forward by
+// linearity and takes the scale from |a|^2 - sum |h|^2, which cancels when h_{t+1,t} << |a_t| -- the known error growth of
+// pipelined Krylov sweeps.  The stored vectors' measured norms nu_i say when that happened: all conversions are exact in nu,
+// but a nu far from 1 means the recurrence lost digits.
+bool onepass_drifted(const qp_krylov* q, int m, int m_eff) {
+  double drift = 0.0;
+  for (int i = 0; i <= m_eff && i <= m; ++i)
+    if (!(i == m_eff && m_eff < m)) drift = std::max(drift, std::fabs(q->h_nu[i] - 1.0));    // (the vector of a breakdown is unnormalised by design)
+  return drift > kOnepassNormDrift;
+}
+
+enum class Sweep { small, onepass, multilaunch };
+
+// small plan fits -> small; else one-pass wanted, allowed and fits -> one-pass; else multi-launch.  Allowed: only an extended
+// low-synchronisation sweep for a caller that divides its combination coefficients by the stored vectors' norms (newton!).
+// Wanted: by the knob, or by size -- basis + matrix beyond the Infinity Cache.
+Sweep choose_sweep(const qp_operator* op, const qp_krylov* q, int m, bool extended, bool scaled_basis_ok, qp::SmallArgs* plan) {
+  const qp_ctx* ctx = op->ctx;
+  if (small_sweep_fits(op, q, m, plan)) return Sweep::small;
+  const double sweep_bytes = 16.0 * (double)q->n * (m + 3) + (op->A.vals_r ? 12.0 : 20.0) * (double)op->A.stored;
+  const bool wanted = ctx->tun.arnoldi_onepass >= 2 || (ctx->tun.arnoldi_onepass == 1 && sweep_bytes > 224.0 * 1024 * 1024);
+  const bool allowed = extended && scaled_basis_ok && ctx->tun.arnoldi_mode == 1;
+  if (wanted && allowed && qp::arnoldi_onepass_fits(op->A, m, q->nvec)) return Sweep::onepass;
+  return Sweep::multilaunch;
+}
+
+}  // namespace
+
 static int arnoldi_impl(qp_operator* op, qp_krylov* q, int m, const qp_state* psi, double dt, int extended,
                         double norm_min, qp_c128* Hess, int ldh, int* m_out, double* beta_out,
                         const ColumnHook* on_column = nullptr, bool scaled_basis_ok = false) {
@@ -281,216 +498,37 @@ static int arnoldi_impl(qp_operator* op, qp_krylov* q, int m, const qp_state* ps
   const int dim = extended ? m + 1 : m;
   if (m < 1 || ldh < dim || q->nvec < m + 1) return qp::fail(QP_E_BAD_ARG, "qp_arnoldi: Hess/q too small for m=%d", m);
   if (op->A.nrows != op->A.ncols || psi->n != op->A.nrows || q->n != psi->n) return qp::fail(QP_E_BAD_ARG, "qp_arnoldi: shape mismatch");
-  qp_ctx* ctx = op->ctx;
-  QP_CHECK(use(ctx));
-  const int ldd = q->nvec;
+  QP_CHECK(use(op->ctx));
   std::memset(Hess, 0, sizeof(qp_c128) * (size_t)ldh * ldh);                                      // :78
+  q->nu_valid = false;   // (true only after a one-pass sweep that stands)
   qp::SmallArgs plan;
-  bool small = false;
-  bool piped = false;
-  bool fold = false;
-  bool flags = false;   // folded + pipelined sweep: columns are announced through col_flags, not events
-  bool early_last = false;   // the last column also raises its early flag
-  if (ctx->tun.small_nnz > 0 && op->A.nnz <= (int64_t)ctx->tun.small_nnz * (qp::kSmallEptArnoldi / qp::kSmallEpt) &&
-      qp::small_arnoldi_fits(q->n, m)) {
-    int64_t maxrow = 0;
-    for (int64_t r = 0; r < q->n; ++r) maxrow = std::max<int64_t>(maxrow, op->u_rowptr[r + 1] - op->u_rowptr[r]);
-    // the plan of the 16-slot kernels where it exists (same lanes per row, hence the same rounding, as
-    // before the 32-slot variants were added), the larger one only for systems that need it
-    small = qp::small_plan(q->n, maxrow, &plan, qp::kSmallEpt) || qp::small_plan(q->n, maxrow, &plan, qp::kSmallEptArnoldi);
-  }
-  q->nu_valid = false;
-  // (only for a caller that divides its combination coefficients by the stored vectors' norms: newton!)
-  const double sweep_bytes = 16.0 * (double)q->n * (m + 3) + (op->A.vals_r ? 12.0 : 20.0) * (double)op->A.stored;
-  const bool onepass_wanted = ctx->tun.arnoldi_onepass >= 2 || (ctx->tun.arnoldi_onepass == 1 && sweep_bytes > 224.0 * 1024 * 1024);
-  if (!small && extended && scaled_basis_ok && ctx->tun.arnoldi_mode == 1 && onepass_wanted && qp::arnoldi_onepass_fits(op->A, m, q->nvec)) {
-    QP_CHECK(arnoldi_onepass(op, q, m, psi, dt, norm_min, Hess, ldh, m_out, beta_out, on_column));
+  Sweep sweep = choose_sweep(op, q, m, extended != 0, scaled_basis_ok, &plan);
+  if (sweep == Sweep::onepass) {
+    QP_CHECK(onepass_sweep(op, q, m, psi, dt, norm_min, Hess, ldh, m_out, beta_out, on_column));
     ++q->n_onepass;
-    // The one-pass sweep never applies H to the new basis vector itself: it carries a_{t+1} = s (H a_t - sum gamma_i q_i) forward by
-    // linearity and takes the scale from |a|^2 - sum |h|^2, which cancels when h_{t+1,t} << |a_t| -- the known error growth of
-    // pipelined Krylov sweeps.  The stored vectors' measured norms nu_i say when that happened: all conversions are exact in nu,
-    // but a nu far from 1 means the recurrence lost digits.  Then the sweep is done again in the two-pass form (the column
-    // hook is idempotent: it recomputes the Ritz values of the leading blocks from the new columns).
-    double drift = 0.0;
-    for (int i = 0; i <= *m_out && i <= m; ++i)
-      if (!(i == *m_out && *m_out < m)) drift = std::max(drift, std::fabs(q->h_nu[i] - 1.0));    // (the vector of a breakdown is unnormalised by design)
-    if (!(drift > kOnepassNormDrift) && ctx->tun.arnoldi_onepass != 3) return QP_OK;
+    if (!onepass_drifted(q, m, *m_out) && op->ctx->tun.arnoldi_onepass != 3) return QP_OK;
+    // drifted (or knob value 3): the sweep is done again in the two-pass form (the column hook is idempotent: it recomputes the
+    // Ritz values of the leading blocks from the new columns)
     ++q->n_onepass_redone;
     q->nu_valid = false;
     std::memset(Hess, 0, sizeof(qp_c128) * (size_t)ldh * ldh);
+    sweep = Sweep::multilaunch;
   }
-  if (small) {
-    // all m columns in one persistent single-workgroup launch (kernels_small.hip: arnoldi_small_kernel)
-    QP_CHECK(operator_csr_mirror(op, false));
-    qp::SmallArnoldiArgs a;
-    a.n = q->n;
-    a.lanes = plan.lanes;
-    a.ent = plan.ent;
-    a.rows_per_group = plan.rows_per_group;
-    a.rowptr = op->m_rowptr;
-    a.cols = op->m_cols;
-    a.map = op->m_map;
-    a.vals = op->A.vals;
-    a.start = psi->d;
-    a.Q = q->Q;
-    a.hess = q->hess_dev;
-    a.norms = q->norms_dev;
-    a.ldd = ldd;
-    a.m = m;
-    a.extended = extended;
-    a.dt = dt;
-    a.norm_min = norm_min;
-    a.normalize_start = beta_out ? 1 : 0;     // the kernel also zero-fills hess / norms
-    QP_CHECK(qp::launch_arnoldi_small(ctx->stream, a, &ctx->stats));
-    q->gram_rows = 0;
-  } else {
-    piped = on_column != nullptr;
-    // Hessenberg entries and norms go straight into the pinned host buffers (nothing of an earlier
-    // sweep is in flight: every sweep ends with a synchronisation)
-    std::memset(q->h_hess, 0, sizeof(double2) * (size_t)ldd * ldd);
-    std::memset(q->h_norms, 0, sizeof(double) * (size_t)ldd);
-    QP_HIP(hipMemsetAsync(q->ticket, 0, sizeof(unsigned), ctx->stream));
-    QP_HIP(hipMemcpyAsync(q->q(0), psi->d, (size_t)q->n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));  // :79
-    if (beta_out) {
-      cplx n2;
-      QP_CHECK(dot_sync(ctx, q->q(0), q->q(0), q->n, &n2));
-      *beta_out = std::sqrt(n2.real());
-      QP_CHECK(qp::launch_scal(ctx->stream, q->q(0), make_double2(1.0 / *beta_out, 0.0), q->n, &ctx->stats));
-    }
-    if (piped) {
-      while ((int)q->col_events.size() < m) {
-        hipEvent_t e;
-        QP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        q->col_events.push_back(e);
-      }
-    }
-    // "norm + scale" of column j is done by the mat-vec of column j + 1 (it scales its row
-    // sums by 1 / |q_j| and stores the normalised q_j as it goes; src/arnoldi.jl:89-96 applied on the fly), so a
-    // column is mat-vec + projection only.  The unnormalised vectors ping-pong between two scratch vectors.
-    fold = op->A.format != QP_FMT_MATFREE && m > 1;
-    if (fold && !q->raw[0]) {
-      QP_CHECK(dev_alloc(&q->raw[0], (size_t)q->n));
-      QP_CHECK(dev_alloc(&q->raw[1], (size_t)q->n));
-    }
-    flags = fold && piped;
-    if (flags) {      // a new sequence number per sweep: the columns announce themselves with it
-      q->seq = q->seq + 1 == 0 ? 1 : q->seq + 1;
-    }
-    auto enqueue_columns = [&]() -> int {
-    for (int j = 0; j < m; ++j) {
-      double2* hcol = q->hess_map + (size_t)j * ldd;
-      if (fold) {
-        FoldArgs fa{q->part + (size_t)(j & 1) * kRedBlocks, j > 0 ? q->hess_map + (size_t)(j - 1) * ldd + j : nullptr,
-                    j > 0 ? q->norms_map + (j - 1) : nullptr, norm_min, (flags && j > 0) ? q->col_flags_map + (j - 1) : nullptr,
-                    q->seq};
-        // The hook of the LAST column is the one the device waits for (the others run while it works on later columns):
-        // its Hessenberg block does not contain the column's norm, so it may start as soon as the projection kernel has
-        // solved for the coefficients -- while that kernel still streams the basis.
-        if (flags && j + 1 == m && j > 0) {
-          fa.early_flag = q->col_flags_map + q->nvec + j;
-          fa.early_armed = &early_last;
-        }
-        QP_CHECK(arnoldi_column(op, q, j, dt, hcol, j == 0 ? q->q(0) : q->raw[j & 1], q->raw[(j + 1) & 1], j > 0 ? &fa : nullptr));
-        if (j + 1 == m) {   // the last vector: normalised into the basis (extended), or handed over as it is
-          if (extended) {
-            hipLaunchKernelGGL(norm_guard_scale_kernel, dim3(guard_grid(q->n)), dim3(qp::kThreads), 0, ctx->stream, q->q(j + 1),
-                               q->part + (size_t)((j + 1) & 1) * kRedBlocks, hcol + (j + 1), q->norms_map + j, dt, norm_min,
-                               q->n, (const double2*)q->raw[(j + 1) & 1], flags ? q->col_flags_map + j : (unsigned*)nullptr, q->seq);
-            QP_HIP(hipGetLastError());
-            ctx->stats.n_launch++;
-          } else {
-            QP_HIP(hipMemcpyAsync(q->q(j + 1), q->raw[(j + 1) & 1], (size_t)q->n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
-          }
-        }
-      } else {
-        QP_CHECK(arnoldi_column(op, q, j, dt, hcol));
-        if ((j + 1 < m) || extended) {                                                               // :88-97
-          hipLaunchKernelGGL(norm_guard_scale_kernel, dim3(guard_grid(q->n)), dim3(qp::kThreads), 0, ctx->stream, q->q(j + 1),
-                             q->part + (size_t)((j + 1) & 1) * kRedBlocks, hcol + (j + 1), q->norms_map + j, dt, norm_min,
-                             q->n, (const double2*)q->q(j + 1), (unsigned*)nullptr, 0u);
-          QP_HIP(hipGetLastError());
-          ctx->stats.n_launch++;
-        }
-      }
-      if (piped && !flags) QP_HIP(hipEventRecord(q->col_events[j], ctx->stream));
-    }
+  SweepShape sw;
+  if (sweep == Sweep::small) {
+    sw.extended = extended != 0;   // columns arrive together at the end of the stream: nothing to overlap a hook with
+    QP_CHECK(enqueue_small_sweep(op, q, plan, m, psi, dt, extended, norm_min, beta_out != nullptr));
+    QP_CHECK(collect_columns(q, m, sw, norm_min, Hess, ldh, nullptr, m_out));
+    if (beta_out) *beta_out = q->h_norms[q->nvec - 1];
     return QP_OK;
-    };
-    QP_CHECK(enqueue_columns());
   }
-  const cplx* hh = reinterpret_cast<const cplx*>(q->h_hess);
-  const double* hn = q->h_norms;
-  if (small) {
-    // one download of the Hessenberg matrix and the norms, into pinned memory
-    QP_HIP(hipMemcpyAsync(q->h_hess, q->hess_dev, (size_t)ldd * ldd * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
-    QP_HIP(hipMemcpyAsync(q->h_norms, q->norms_dev, (size_t)ldd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if (!piped) QP_HIP(hipStreamSynchronize(ctx->stream));
-  if (small && beta_out) *beta_out = hn[ldd - 1];   // written by the kernel (slot ldd - 1 is never a column's)
-  int m_eff = m;
-  int hook_rc = QP_OK;
-  // wait until column j is complete on the host: an event, or (folded sweep) the flag that the mat-vec of
-  // column j + 1 sets after the column's last entries -- the last column has no successor: stream end
-  auto wait_column = [&](int j) -> int {
-    if (!piped) return QP_OK;
-    if (!flags) {
-      QP_HIP(hipEventSynchronize(q->col_events[j]));
-      return QP_OK;
-    }
-    if (j + 1 == m && !extended) {   // no kernel after the last column that could announce it
-      QP_HIP(hipStreamSynchronize(ctx->stream));
-      return QP_OK;
-    }
-    const auto t_begin = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (__atomic_load_n(&q->col_flags[j], __ATOMIC_ACQUIRE) != q->seq) {
-      QP_CPU_RELAX();
-      if ((++spins & 0xfffffu) == 0 &&
-          std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count() > 5.0) {
-        // never spin for good: fall back to the stream and look once more
-        QP_HIP(hipStreamSynchronize(ctx->stream));
-        if (__atomic_load_n(&q->col_flags[j], __ATOMIC_ACQUIRE) != q->seq)
-          return qp::fail(QP_E_INTERNAL, "Arnoldi column %d never announced itself to the host", j);
-      }
-    }
-    return QP_OK;
-  };
-  auto copy_column = [&](int j, int rows) {
-    for (int i = 0; i < rows; ++i) {
-      cplx v = hh[(size_t)j * ldd + i];
-      Hess[(size_t)j * ldh + i] = qp_c128{v.real(), v.imag()};
-    }
-  };
-  for (int j = 0; j < m; ++j) {
-    const int rows = std::min(j + 2, dim);
-    bool hooked = false;
-    if (early_last && j + 1 == m) {   // coefficients first, hook, then the norm
-      unsigned spins = 0;
-      const unsigned* ef = q->col_flags + q->nvec + j;
-      while (__atomic_load_n(ef, __ATOMIC_ACQUIRE) != q->seq && ++spins < (1u << 24)) QP_CPU_RELAX();
-      if (__atomic_load_n(ef, __ATOMIC_ACQUIRE) == q->seq) {
-        copy_column(j, j + 1);
-        if ((hook_rc = (*on_column)(j)) != QP_OK) break;
-        hooked = true;
-      }
-    }
-    QP_CHECK(wait_column(j));
-    if (j + 1 == m) q->t_last_column = std::chrono::steady_clock::now();
-    copy_column(j, rows);
-    if (piped && !hooked && (hook_rc = (*on_column)(j)) != QP_OK) break;
-    if (((j + 1 < m) || extended) && hn[j] < norm_min) {  // dimensionality exhausted  :91-95
-      m_eff = j + 1;
-      break;
-    }
-  }
-  // the columns after a breakdown are discarded: wait for them.  (A complete folded sweep needs no wait: its last
-  // column announced itself, and what the device still does -- normalising the last vector -- is consumed in stream order.)
-  if (piped && !(flags && extended && m_eff == m && hook_rc == QP_OK)) QP_HIP(hipStreamSynchronize(ctx->stream));
-  if (hook_rc != QP_OK) return hook_rc;
-  *m_out = m_eff;
-  return QP_OK;
+  // columns are awaited one by one only for a hook's sake
+  QP_CHECK(enqueue_multilaunch_sweep(op, q, m, psi, dt, extended != 0, norm_min, beta_out, on_column != nullptr, &sw));
+  return collect_columns(q, m, sw, norm_min, Hess, ldh, on_column, m_out);
   QP_CATCH
 }
+
+extern "C" {
 
 int qp_arnoldi(qp_operator* op, qp_krylov* q, int m, const qp_state* psi, double dt, int extended, double norm_min,
                qp_c128* Hess, int ldh, int* m_out) {
@@ -523,13 +561,9 @@ int qp_arnoldi_extend(qp_operator* op, qp_krylov* q, int m, double dt, double no
   QP_CATCH
 }
 
-}  // extern "C"
-
 // ---------------------------------------------------------------------------
 // building blocks of a row-partitioned Arnoldi / Newton (the caller owns the collectives)
 // ---------------------------------------------------------------------------
-extern "C" {
-
 int qp_krylov_vec(qp_krylov* q, int i, qp_state** out) {
   QP_TRY
   if (!q || !out || i < 0 || i >= q->nvec) return qp::fail(QP_E_BAD_ARG, "qp_krylov_vec: bad arguments");
@@ -564,12 +598,8 @@ int qp_krylov_normalize(qp_krylov* q, int j, double dt, double norm_min, const q
   if (!q || !norm_partials || !hess_norm || j < 0 || j + 1 >= q->nvec || norm_partials->n < kRedBlocks || hess_norm->n < 2)
     return qp::fail(QP_E_BAD_ARG, "qp_krylov_normalize: bad arguments");
   QP_CHECK(use(q->ctx));
-  hipLaunchKernelGGL(norm_guard_scale_kernel, dim3(guard_grid(q->n)), dim3(qp::kThreads), 0, q->ctx->stream, q->q(j + 1),
-                     norm_partials->d, hess_norm->d, reinterpret_cast<double*>(hess_norm->d + 1), dt, norm_min, q->n,
-                     (const double2*)q->q(j + 1), (unsigned*)nullptr, 0u);
-  QP_HIP(hipGetLastError());
-  q->ctx->stats.n_launch++;
-  return QP_OK;
+  return qp::launch_norm_guard_scale(q->ctx->stream, q->q(j + 1), q->q(j + 1), norm_partials->d, hess_norm->d,
+                                     reinterpret_cast<double*>(hess_norm->d + 1), dt, norm_min, q->n, nullptr, 0u, &q->ctx->stats);
   QP_CATCH
 }
 
@@ -586,45 +616,9 @@ int qp_combine(qp_state* out, int use_out, qp_c128 s0, qp_krylov* q, int first, 
   QP_CATCH
 }
 
-}  // extern "C"
-
-// norm + guarded scale: lmul!(1/h) only when h >= norm_min (src/arnoldi.jl:89-96); the
-// raw norm is kept so that the host can detect breakdown also for dt < 0.
-// (w_in != w: the scaled -- or, past a breakdown, the unscaled -- vector goes to w, w_in is left alone)
-// (flag != NULL: host-visible announcement that the slots are written, see PlainEpi::flag)
-__global__ __launch_bounds__(qp::kThreads) void norm_guard_scale_kernel(double2* w, const double2* __restrict__ part_in,
-                                                                        double2* hess_slot, double* norm_slot, double dt,
-                                                                        double norm_min, int64_t n, const double2* w_in,
-                                                                        unsigned* flag, unsigned flag_value) {
-  __shared__ double2 lds[qp::kThreads / 64];
-  double2 v = part_in[threadIdx.x];
-  for (int o = 32; o > 0; o >>= 1) {
-    v.x += __shfl_down(v.x, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s2 = lds[0].x + lds[1].x + lds[2].x + lds[3].x;
-  const double h = sqrt(s2);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    *hess_slot = make_double2(dt * h, 0.0);
-    *norm_slot = h;
-    if (flag) __hip_atomic_store(flag, flag_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  if (h < norm_min && w_in == w) return;
-  const double inv = (h < norm_min) ? 1.0 : 1.0 / h;
-  for (int64_t i = (int64_t)blockIdx.x * qp::kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * qp::kThreads) {
-    double2 t = w_in[i];
-    t.x *= inv;
-    t.y *= inv;
-    w[i] = t;
-  }
-}
-
 // ---------------------------------------------------------------------------
 // Newton
 // ---------------------------------------------------------------------------
-extern "C" {
-
 int qp_newton_create(qp_ctx* ctx, int64_t n, int m_max, qp_newton** out) {
   QP_TRY
   if (!ctx || !out || n < 0) return qp::fail(QP_E_BAD_ARG, "qp_newton_create: bad arguments");
@@ -655,9 +649,9 @@ int qp_newton_destroy(qp_newton* w) {
   (void)hipSetDevice(w->ctx->device);
   (void)hipStreamSynchronize(w->ctx->stream);
   qp_krylov_destroy(w->q);
-  if (w->v) (void)hipFree(w->v);
-  if (w->npart) (void)hipFree(w->npart);
-  if (w->h_npart) (void)hipHostFree(w->h_npart);
+  dev_release(w->v);
+  dev_release(w->npart);
+  host_release(w->h_npart);
   delete w;
   return QP_OK;
   QP_CATCH
@@ -670,6 +664,52 @@ int qp_newton_get_coeffs(const qp_newton* w, qp_c128* a, qp_c128* leja, int cap)
     if (a) a[i] = qp_c128{w->a[i].real(), w->a[i].imag()};
     if (leja) leja[i] = qp_c128{w->leja[i].real(), w->leja[i].imag()};
   }
+  return QP_OK;
+}
+
+// m more Leja points from the Ritz values of this restart (src/newton.jl:306; prod_folded: the head of every candidate's product
+// chain, where the hook built it while the columns arrived) and the Newton coefficients that go with them (:313-314)
+static int newton_extend_points(qp_newton* w, std::vector<cplx>& ritz, int m, const qp::ScaledProd* prod_folded, int func_id,
+                                qp_func_cb cb, void* user, bool ranges, int* n_leja, int* n_a, qp_newton_stats* st) {
+  auto ms_since = [](std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  };
+  if ((int)w->leja.size() < *n_leja + m) w->leja.resize((size_t)2 * (*n_leja + m), cplx(0));  // :105-110
+  auto t0 = std::chrono::steady_clock::now();
+  {
+    const qp::ScopedRange leja_range(ranges, "get Leja points");
+    qp::extend_leja(w->leja.data(), *n_leja, ritz.data(), (int)ritz.size(), m, prod_folded);
+  }
+  st->ms_leja += ms_since(t0);
+  *n_leja += m;
+  if ((int)w->a.size() < *n_leja) w->a.resize((size_t)2 * *n_leja, cplx(0));         // :187-192
+  t0 = std::chrono::steady_clock::now();
+  int rc;
+  {
+    const qp::ScopedRange coeff_range(ranges, "get Newton coeffs");
+    rc = qp::extend_newton_coeffs(w->a.data(), *n_a, w->leja.data(), func_id, cb, user, *n_leja, w->radius);
+  }
+  st->ms_coeffs += ms_since(t0);
+  if (rc == QP_E_DIVDIFF_UNDERFLOW) return qp::fail(rc, "Divided differences too small");
+  if (rc != QP_OK) return qp::fail(rc, "extend_newton_coeffs failed (radius=%g)", w->radius);
+  *n_a = *n_leja;
+  return QP_OK;
+}
+
+// Psi = (accumulate ? Psi : 0) + sum_{i<m} P_i q_i  (:346-352)  and  v = sum_{i<=m} R_i q_i  (q_0 is the start vector of this
+// sweep): one pass over the basis; fixed-size coefficient blocks, else one by one.  *norm_psi = |Psi| afterwards.
+static int newton_update_states(qp_ctx* ctx, qp_newton* w, qp_state* psi, bool accumulate, int m, double* norm_psi) {
+  const double2 *P = reinterpret_cast<const double2*>(w->P.data()), *R = reinterpret_cast<const double2*>(w->R.data());
+  if (!qp::launch_combine2_vecs(ctx->stream, psi->d, accumulate ? 1 : 0, m, P, w->v, m + 1, R, w->q->q(0), w->n, w->npart, w->n,
+                                &ctx->stats)) {
+    QP_CHECK(qp::launch_combine_vecs(ctx->stream, psi->d, accumulate ? 1 : 0, make_double2(1.0, 0.0), w->q->q(0), w->n, m, P, w->npart,
+                                     w->n, &ctx->stats));
+    QP_CHECK(qp::launch_combine_vecs(ctx->stream, w->v, 0, make_double2(1.0, 0.0), w->q->q(0), w->n, m + 1, R, nullptr, w->n,
+                                     &ctx->stats));
+  }
+  QP_HIP(hipMemcpyAsync(w->h_npart, w->npart, kRedBlocks * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+  QP_HIP(hipStreamSynchronize(ctx->stream));
+  *norm_psi = std::sqrt(sum_partials(w->h_npart).real());
   return QP_OK;
 }
 
@@ -690,14 +730,13 @@ int qp_newton_step(qp_newton* w, qp_operator* op, qp_state* psi, double dt, int 
   std::fill(w->a.begin(), w->a.end(), cplx(0));                         // :254-255
   std::fill(w->leja.begin(), w->leja.end(), cplx(0));
   const int ldh = m_max + 1;
-  std::vector<cplx>&Hess = w->Hess, &R = w->R, &P = w->P, &Rn = w->Rn, &ritz = w->ritz;
+  std::vector<cplx>&Hess = w->Hess, &ritz = w->ritz;
   Hess.assign((size_t)ldh * ldh, cplx(0));
-  int n_a = 0, n_leja = 0, s = 0, n_matvec = 0;
-  double last_relerr = 0, norm_psi = 0;
+  int n_a = 0, n_leja = 0, s = 0;
+  qp_newton_stats st{};   // filled as the step goes, handed out at its end
   qp_state vstate{ctx, w->v, w->n, false};
   // v = Psi / beta, beta = |Psi| (:268-272) is done by the first Arnoldi sweep itself (q_0)
   double beta = 0.0;
-  double ms_arnoldi = 0, ms_eig = 0, ms_leja = 0, ms_coeffs = 0, ms_poly = 0, ms_update = 0, ms_exposed = 0;
   const int onepass0 = w->q->n_onepass, redone0 = w->q->n_onepass_redone;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto ms_since = [](std::chrono::steady_clock::time_point t0) {
@@ -719,15 +758,15 @@ int qp_newton_step(qp_newton* w, qp_operator* op, qp_state* psi, double dt, int 
       auto t1 = now();
       const qp::ScopedRange eig_range(ranges, "diagonalize_hessenberg_matrix");   // src/newton.jl:296
       const size_t off = (size_t)j * (j + 1) / 2;
-      const int st = qp::diagonalize_hessenberg_block(Hess.data(), ldh, j + 1, ritz.data() + off);
+      const int rc = qp::diagonalize_hessenberg_block(Hess.data(), ldh, j + 1, ritz.data() + off);
       ms_eig_sweep += ms_since(t1);
-      if (st == QP_OK && n_leja > 0) {
+      if (rc == QP_OK && n_leja > 0) {
         t1 = now();
         for (int i = 0; i <= j; ++i) lprod[off + i] = qp::leja_fold_candidate(w->leja.data(), n_leja, ritz[off + i]);
         ms_fold_sweep += ms_since(t1);
       }
       blocks_done = j + 1;
-      return st == QP_OK ? QP_OK : qp::fail(QP_E_INTERNAL, "Hessenberg QR did not converge");
+      return rc == QP_OK ? QP_OK : qp::fail(QP_E_INTERNAL, "Hessenberg QR did not converge");
     };
     {
       const qp::ScopedRange arnoldi_range(ranges, "arnoldi!");                       // src/newton.jl:276
@@ -735,10 +774,10 @@ int qp_newton_step(qp_newton* w, qp_operator* op, qp_state* psi, double dt, int 
                             reinterpret_cast<qp_c128*>(Hess.data()), ldh, &m, s == 0 ? &beta : nullptr,
                             ctx->tun.newton_pipeline ? &eig_block : nullptr, true));
     }
-    ms_arnoldi += ms_since(t0) - ms_eig_sweep - ms_fold_sweep;
-    ms_eig += ms_eig_sweep;
-    ms_leja += ms_fold_sweep;
-    n_matvec += m_req;
+    st.ms_arnoldi += ms_since(t0) - ms_eig_sweep - ms_fold_sweep;
+    st.ms_eig += ms_eig_sweep;
+    st.ms_leja += ms_fold_sweep;
+    st.n_matvec += m_req;
     if (m == 1 && s == 0) {                                                          // :289-295
       const cplx lam = beta * Hess[0];
       const cplx f = qp::eval_func(func_id, cb, user, lam);
@@ -750,97 +789,33 @@ int qp_newton_step(qp_newton* w, qp_operator* op, qp_state* psi, double dt, int 
       QP_CHECK(eig_block(j));
     ritz.resize((size_t)m * (m + 1) / 2);
     const bool folded = n_leja > 0;   // (the products do not depend on m: valid also after a breakdown)
-    ms_eig += ms_since(t0);
+    st.ms_eig += ms_since(t0);
     if (s == 0) {                                                                    // :301-303, :67-70
       double rmax = 0;
       for (auto& z : ritz) rmax = std::max(rmax, std::abs(z));
       w->radius = 1.2 * rmax;
     }
     const int n_s = n_leja;                                                          // :307
-    if ((int)w->leja.size() < n_leja + m) w->leja.resize((size_t)2 * (n_leja + m), cplx(0));  // :105-110
-    t0 = now();
-    {
-      const qp::ScopedRange leja_range(ranges, "get Leja points");                   // src/newton.jl:306
-      qp::extend_leja(w->leja.data(), n_leja, ritz.data(), (int)ritz.size(), m, folded ? lprod.data() : nullptr);
-    }
-    ms_leja += ms_since(t0);
-    n_leja += m;
-    if ((int)w->a.size() < n_leja) w->a.resize((size_t)2 * n_leja, cplx(0));         // :187-192
-    {
-      t0 = now();
-      int st;
-      {
-        const qp::ScopedRange coeff_range(ranges, "get Newton coeffs");              // src/newton.jl:313
-        st = qp::extend_newton_coeffs(w->a.data(), n_a, w->leja.data(), func_id, cb, user, n_leja, w->radius);  // :314
-      }
-      ms_coeffs += ms_since(t0);
-      if (st == QP_E_DIVDIFF_UNDERFLOW) return qp::fail(st, "Divided differences too small");
-      if (st != QP_OK) return qp::fail(st, "extend_newton_coeffs failed (radius=%g)", w->radius);
-      n_a = n_leja;
-    }
-    // Newton polynomial in the extended Hessenberg matrix                           :328-343
+    QP_CHECK(newton_extend_points(w, ritz, m, folded ? lprod.data() : nullptr, func_id, cb, user, ranges, &n_leja, &n_a, &st));
+    // Newton polynomial in the extended Hessenberg matrix (:328-343), then the starting vector of the next restart (:356-367):
+    // host algebra (host_numerics.cpp) that leaves the coefficients of Psi in P and those of v in R, in the stored basis
     if (ranges) qp::range_push("evaluate polynomial");                               // src/newton.jl:328 (closed after the update below)
     t0 = now();
-    const int mp = m + 1;
-    R.assign(mp, cplx(0));
-    P.assign(mp, cplx(0));
-    Rn.assign(mp, cplx(0));
-    R[0] = beta;
-    P[0] = w->a[n_s] * beta;
-    auto apply = [&](cplx z) {
-      for (int i = 0; i < mp; ++i) {
-        cplx acc = 0;
-        for (int k = 0; k < mp; ++k) acc += Hess[(size_t)k * ldh + i] * R[k];
-        Rn[i] = (acc - z * R[i]) / w->radius;
-      }
-      std::swap(R, Rn);
-    };
-    for (int k = 1; k <= m - 1; ++k) {
-      apply(w->leja[n_s + k - 1]);
-      for (int i = 0; i < mp; ++i) P[i] += w->a[n_s + k] * R[i];
-    }
-    ms_poly += ms_since(t0);
+    qp::newton_restart_poly(Hess.data(), ldh, m, w->a.data() + n_s, w->leja.data() + n_s, w->radius, beta, w->P, w->R, w->Rn);
+    st.ms_poly += ms_since(t0);
     t0 = now();
-    // starting vector of the next restart (host part)                                :356-367
-    apply(w->leja[n_s + m - 1]);
-    double b2 = 0;
-    for (int i = 0; i < mp; ++i) {
-      const double ab = std::abs(R[i]);
-      b2 += ab * ab;
-    }
-    beta = std::sqrt(b2);
-    for (int i = 0; i < mp; ++i) R[i] *= (1.0 / beta);
-    // Psi = (s == 0 ? 0 : Psi) + sum_{i<m} P_i q_i  (:346-352)  and  v = sum_{i<=m} R_i q_i  (q_0 is the
-    // start vector of this sweep): one pass over the basis; fixed-size coefficient blocks, else one by one
-    if (w->q->nu_valid) {
-      // one-pass sweep: the stored basis vectors have norm nu_i (not exactly one): coefficients in the orthonormal basis -> stored basis
-      for (int i = 0; i < mp; ++i) {
-        const double nu = w->q->h_nu[i];
-        const double inv = nu > 0.0 ? 1.0 / nu : 0.0;
-        if (i < m) P[i] *= inv;
-        R[i] *= inv;
-      }
-    }
-    ms_exposed += ms_since(w->q->t_last_column);
-    if (!qp::launch_combine2_vecs(ctx->stream, psi->d, s == 0 ? 0 : 1, m, reinterpret_cast<const double2*>(P.data()), w->v,
-                                  m + 1, reinterpret_cast<const double2*>(R.data()), w->q->q(0), w->n, w->npart, w->n,
-                                  &ctx->stats)) {
-      QP_CHECK(qp::launch_combine_vecs(ctx->stream, psi->d, s == 0 ? 0 : 1, make_double2(1.0, 0.0), w->q->q(0), w->n, m,
-                                       reinterpret_cast<const double2*>(P.data()), w->npart, w->n, &ctx->stats));
-      QP_CHECK(qp::launch_combine_vecs(ctx->stream, w->v, 0, make_double2(1.0, 0.0), w->q->q(0), w->n, m + 1,
-                                       reinterpret_cast<const double2*>(R.data()), nullptr, w->n, &ctx->stats));
-    }
-    QP_HIP(hipMemcpyAsync(w->h_npart, w->npart, kRedBlocks * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
-    QP_HIP(hipStreamSynchronize(ctx->stream));
-    norm_psi = std::sqrt(sum_partials(w->h_npart).real());
+    beta = qp::newton_restart_next(Hess.data(), ldh, m, w->leja[n_s + m - 1], w->radius, w->q->nu_valid ? w->q->h_nu : nullptr, w->P,
+                                   w->R, w->Rn);
+    st.ms_exposed += ms_since(w->q->t_last_column);
+    QP_CHECK(newton_update_states(ctx, w, psi, s > 0, m, &st.norm_psi));
     if (ranges) qp::range_pop();
-    ms_update += ms_since(t0);
-    last_relerr = beta * std::abs(w->a[n_a - 1]) / (1 + norm_psi);                    // :370
-    if (last_relerr < relerr) break;
+    st.ms_update += ms_since(t0);
+    st.last_relerr = beta * std::abs(w->a[n_a - 1]) / (1 + st.norm_psi);              // :370
+    if (st.last_relerr < relerr) break;
     s += 1;
     if (s > max_restarts) {                                                           // :375
       w->restarts = s;
-      return qp::fail(QP_E_MAX_RESTARTS, "newton!: s=%d exceeds max_restarts=%d (relerr=%g)", s, max_restarts, last_relerr);
+      return qp::fail(QP_E_MAX_RESTARTS, "newton!: s=%d exceeds max_restarts=%d (relerr=%g)", s, max_restarts, st.last_relerr);
     }
   }
   w->restarts = s;
@@ -848,32 +823,46 @@ int qp_newton_step(qp_newton* w, qp_operator* op, qp_state* psi, double dt, int 
   w->n_a = n_a;
   ctx->stats.n_newton_steps++;
   ctx->stats.n_restarts += s;
-  if (stats) {
-    stats->restarts = s;
-    stats->n_a = n_a;
-    stats->n_leja = n_leja;
-    stats->m_last = m;
-    stats->n_matvec = n_matvec;
-    stats->radius = w->radius;
-    stats->last_relerr = last_relerr;
-    stats->norm_psi = norm_psi;
-    stats->ms_arnoldi = ms_arnoldi;
-    stats->ms_eig = ms_eig;
-    stats->ms_leja = ms_leja;
-    stats->ms_coeffs = ms_coeffs;
-    stats->ms_poly = ms_poly;
-    stats->ms_update = ms_update;
-    stats->ms_exposed = ms_exposed;
-    stats->sweeps_onepass = w->q->n_onepass - onepass0;
-    stats->sweeps_onepass_redone = w->q->n_onepass_redone - redone0;
-  }
+  st.restarts = s;
+  st.n_a = n_a;
+  st.n_leja = n_leja;
+  st.m_last = m;
+  st.radius = w->radius;
+  st.sweeps_onepass = w->q->n_onepass - onepass0;
+  st.sweeps_onepass_redone = w->q->n_onepass_redone - redone0;
+  if (stats) *stats = st;
   return QP_OK;
   QP_CATCH
 }
 
+}  // extern "C"
+
 // ---------------------------------------------------------------------------
 // SpectralRange
 // ---------------------------------------------------------------------------
+namespace {
+
+// Ritz values of the leading m x m block of Hess into ev, and their extent: smallest and largest real part, largest |imaginary part|
+struct RitzExtent {
+  double lo, hi, im;
+};
+int ritz_extent(const std::vector<cplx>& Hess, int ldh, int m, std::vector<cplx>& ev, RitzExtent* x) {
+  ev.assign(m, cplx(0));
+  if (qp::diagonalize_hessenberg(Hess.data(), ldh, m, false, ev.data()) != QP_OK)
+    return qp::fail(QP_E_INTERNAL, "Hessenberg QR did not converge");
+  *x = RitzExtent{ev[0].real(), ev[0].real(), std::fabs(ev[0].imag())};
+  for (auto& z : ev) {
+    x->lo = std::min(x->lo, z.real());
+    x->hi = std::max(x->hi, z.real());
+    x->im = std::max(x->im, std::fabs(z.imag()));
+  }
+  return QP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int qp_ritzvals(qp_operator* op, const qp_state* state, int m_min, int m_max, double prec, double norm_min,
                 qp_c128* out, int* n_out) {
   QP_TRY
@@ -885,51 +874,32 @@ int qp_ritzvals(qp_operator* op, const qp_state* state, int m_min, int m_max, do
   if (m_max < m) return qp::fail(QP_E_BAD_ARG, "m_max=%d too small (need >= %d)", m_max, m);
   const int ldh = m_max;
   std::vector<cplx> Hess((size_t)ldh * ldh, cplx(0));
+  qp_c128* H = reinterpret_cast<qp_c128*>(Hess.data());
   qp_krylov* q = nullptr;
   QP_CHECK(qp_krylov_create(ctx, state->n, m_max + 1, &q));
   std::unique_ptr<qp_krylov, int (*)(qp_krylov*)> guard(q, qp_krylov_destroy);
   std::vector<cplx> ev;
-  auto stats3 = [&](double& lo, double& hi, double& im) {
-    lo = ev[0].real();
-    hi = ev[0].real();
-    im = std::fabs(ev[0].imag());
-    for (auto& z : ev) {
-      lo = std::min(lo, z.real());
-      hi = std::max(hi, z.real());
-      im = std::max(im, std::fabs(z.imag()));
-    }
-  };
-  auto diag = [&](int mm) -> int {
-    ev.assign(mm, cplx(0));
-    return qp::diagonalize_hessenberg(Hess.data(), ldh, mm, false, ev.data());
-  };
+  RitzExtent x0, x;
   int m0 = m - 1;
-  QP_CHECK(qp_arnoldi(op, q, m0, state, 1.0, 0, norm_min, reinterpret_cast<qp_c128*>(Hess.data()), ldh, &m0));  // :182
-  if (diag(m0) != QP_OK) return qp::fail(QP_E_INTERNAL, "Hessenberg QR did not converge");
-  double lo0, hi0, im0;
-  stats3(lo0, hi0, im0);
+  QP_CHECK(qp_arnoldi(op, q, m0, state, 1.0, 0, norm_min, H, ldh, &m0));  // :182
+  QP_CHECK(ritz_extent(Hess, ldh, m0, ev, &x0));
   if (m0 == m - 1) {
     int ext = 0;
-    QP_CHECK(qp_arnoldi_extend(op, q, m, 1.0, norm_min, reinterpret_cast<qp_c128*>(Hess.data()), ldh, &ext));  // :190
-    if (diag(m) != QP_OK) return qp::fail(QP_E_INTERNAL, "Hessenberg QR did not converge");
-    double lo, hi, im;
-    stats3(lo, hi, im);
-    double er_lo = (lo0 != 0.0) ? std::fabs(1.0 - lo / lo0) : 0.0;
-    double er_hi = (hi0 != 0.0) ? std::fabs(1.0 - hi / hi0) : 0.0;
-    double ei = (im0 != 0.0) ? std::fabs(1.0 - im / im0) : 0.0;
-    while ((er_lo > prec) || (er_hi > prec) || ((im0 > 1e-14) && ei > prec)) {   // :198
-      lo0 = lo;
-      hi0 = hi;
-      im0 = im;
+    QP_CHECK(qp_arnoldi_extend(op, q, m, 1.0, norm_min, H, ldh, &ext));  // :190
+    QP_CHECK(ritz_extent(Hess, ldh, m, ev, &x));
+    double er_lo = (x0.lo != 0.0) ? std::fabs(1.0 - x.lo / x0.lo) : 0.0;
+    double er_hi = (x0.hi != 0.0) ? std::fabs(1.0 - x.hi / x0.hi) : 0.0;
+    double ei = (x0.im != 0.0) ? std::fabs(1.0 - x.im / x0.im) : 0.0;
+    while ((er_lo > prec) || (er_hi > prec) || ((x0.im > 1e-14) && ei > prec)) {   // :198
+      x0 = x;
       m = m + 1;
       // quirk kept: the reference discards extend_arnoldi!'s return value, so Krylov
       // exhaustion is never detected here (:204-205)
-      QP_CHECK(qp_arnoldi_extend(op, q, m, 1.0, norm_min, reinterpret_cast<qp_c128*>(Hess.data()), ldh, &ext));
-      if (diag(m) != QP_OK) return qp::fail(QP_E_INTERNAL, "Hessenberg QR did not converge");
-      stats3(lo, hi, im);
-      er_lo = std::fabs(1.0 - (lo / lo0));
-      er_hi = std::fabs(1.0 - (hi / hi0));
-      ei = std::fabs(1.0 - (im / im0));
+      QP_CHECK(qp_arnoldi_extend(op, q, m, 1.0, norm_min, H, ldh, &ext));
+      QP_CHECK(ritz_extent(Hess, ldh, m, ev, &x));
+      er_lo = std::fabs(1.0 - (x.lo / x0.lo));   // (quirk kept: unguarded divisions inside the loop, :209-211)
+      er_hi = std::fabs(1.0 - (x.hi / x0.hi));
+      ei = std::fabs(1.0 - (x.im / x0.im));
       if (m == m_max) break;                                                     // :213-216
     }
   }

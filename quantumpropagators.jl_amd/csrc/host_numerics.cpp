@@ -391,6 +391,56 @@ int extend_newton_coeffs(cplx* a, int n_a, const cplx* leja, int func_id, qp_fun
 }
 
 // ---------------------------------------------------------------------------
+// newton!: the polynomial in the extended Hessenberg matrix and the next restart's start vector
+// (the arithmetic and its order are those of the reference; the restart counts depend on them)
+// ---------------------------------------------------------------------------
+// R <- (Hess R - z R) / radius on the (m + 1)-vector R (Hess as a square matrix whose last column is zero)
+static void newton_apply(const cplx* Hess, int ldh, int mp, cplx z, double radius, std::vector<cplx>& R, std::vector<cplx>& Rn) {
+  for (int i = 0; i < mp; ++i) {
+    cplx acc = 0;
+    for (int k = 0; k < mp; ++k) acc += Hess[(size_t)k * ldh + i] * R[k];
+    Rn[i] = (acc - z * R[i]) / radius;
+  }
+  std::swap(R, Rn);
+}
+
+void newton_restart_poly(const cplx* Hess, int ldh, int m, const cplx* a, const cplx* leja, double radius, double beta,
+                         std::vector<cplx>& P, std::vector<cplx>& R, std::vector<cplx>& Rn) {   // src/newton.jl:328-343
+  const int mp = m + 1;
+  R.assign(mp, cplx(0));
+  P.assign(mp, cplx(0));
+  Rn.assign(mp, cplx(0));
+  R[0] = beta;
+  P[0] = a[0] * beta;
+  for (int k = 1; k <= m - 1; ++k) {
+    newton_apply(Hess, ldh, mp, leja[k - 1], radius, R, Rn);
+    for (int i = 0; i < mp; ++i) P[i] += a[k] * R[i];
+  }
+}
+
+double newton_restart_next(const cplx* Hess, int ldh, int m, cplx z_last, double radius, const double* nu, std::vector<cplx>& P,
+                           std::vector<cplx>& R, std::vector<cplx>& Rn) {                        // src/newton.jl:356-367
+  const int mp = m + 1;
+  newton_apply(Hess, ldh, mp, z_last, radius, R, Rn);
+  double b2 = 0;
+  for (int i = 0; i < mp; ++i) {
+    const double ab = std::abs(R[i]);
+    b2 += ab * ab;
+  }
+  const double beta = std::sqrt(b2);
+  for (int i = 0; i < mp; ++i) R[i] *= (1.0 / beta);
+  if (nu) {
+    // one-pass sweep: the stored basis vectors have norm nu_i (not exactly one): coefficients in the orthonormal basis -> stored basis
+    for (int i = 0; i < mp; ++i) {
+      const double inv = nu[i] > 0.0 ? 1.0 / nu[i] : 0.0;
+      if (i < m) P[i] *= inv;
+      R[i] *= inv;
+    }
+  }
+  return beta;
+}
+
+// ---------------------------------------------------------------------------
 // CSC -> CSR (stable counting sort; columns end up ascending within each row because
 // CSC is traversed column by column)
 // ---------------------------------------------------------------------------

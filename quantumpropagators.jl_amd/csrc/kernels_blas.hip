@@ -211,6 +211,60 @@ int launch_norm_scale(hipStream_t s, double2* w, const double2* part_in, double2
   return QP_OK;
 }
 
+}  // namespace qp
+
+// norm + guarded scale: lmul!(1/h) only when h >= norm_min (src/arnoldi.jl:89-96); the
+// raw norm is kept so that the host can detect breakdown also for dt < 0.
+// (w_in != w: the scaled -- or, past a breakdown, the unscaled -- vector goes to w, w_in is left alone)
+// (flag != NULL: host-visible announcement that the slots are written, see PlainEpi::flag)
+// (C linkage, outside the namespace: the plain name under which kernel traces have always shown it)
+extern "C" __global__ __launch_bounds__(qp::kThreads) void norm_guard_scale_kernel(double2* w, const double2* __restrict__ part_in,
+                                                                        double2* hess_slot, double* norm_slot, double dt,
+                                                                        double norm_min, int64_t n, const double2* w_in,
+                                                                        unsigned* flag, unsigned flag_value) {
+  static_assert(qp::kRedBlocks == qp::kThreads && qp::kThreads == 4 * 64, "one partial per thread, one LDS slot for each of four wavefronts");
+  __shared__ double2 lds[qp::kThreads / 64];
+  double2 v = part_in[threadIdx.x];
+  for (int o = 32; o > 0; o >>= 1) {
+    v.x += __shfl_down(v.x, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const double s2 = lds[0].x + lds[1].x + lds[2].x + lds[3].x;
+  const double h = sqrt(s2);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *hess_slot = make_double2(dt * h, 0.0);
+    *norm_slot = h;
+    if (flag) __hip_atomic_store(flag, flag_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  if (h < norm_min && w_in == w) return;
+  const double inv = (h < norm_min) ? 1.0 : 1.0 / h;
+  for (int64_t i = (int64_t)blockIdx.x * qp::kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * qp::kThreads) {
+    double2 t = w_in[i];
+    t.x *= inv;
+    t.y *= inv;
+    w[i] = t;
+  }
+}
+
+namespace qp {
+
+// workgroups of norm_guard_scale_kernel: every one re-reduces the 256 partials, so no more of them than
+// two elements per lane need (the partial order, hence the norm, does not depend on the grid)
+static inline int guard_grid(int64_t n) {
+  return (int)std::max<int64_t>(64, std::min<int64_t>(2048, (n + 2 * qp::kThreads - 1) / (2 * qp::kThreads)));
+}
+
+int launch_norm_guard_scale(hipStream_t s, double2* w, const double2* w_in, const double2* part_in, double2* hess_slot,
+                            double* norm_slot, double dt, double norm_min, int64_t n, unsigned* flag, unsigned flag_value,
+                            Stats* st) {
+  hipLaunchKernelGGL(norm_guard_scale_kernel, dim3(guard_grid(n)), dim3(kThreads), 0, s, w, part_in, hess_slot, norm_slot, dt,
+                     norm_min, n, w_in, flag, flag_value);
+  QP_HIP(hipGetLastError());
+  if (st) st->n_launch++;
+  return QP_OK;
+}
+
 __global__ __launch_bounds__(kThreads) void combine_vecs_kernel(double2* __restrict__ out, int use_out, double2 s0,
                                                                 const double2* __restrict__ Q, int64_t ldq, int m,
                                                                 CoefBlock coefs,

@@ -36,6 +36,16 @@ ScaledProd leja_fold_candidate(const cplx* leja, int n, cplx z);
 cplx eval_func(int func_id, qp_func_cb cb, void* user, cplx z);
 int extend_newton_coeffs(cplx* a, int n_a, const cplx* leja, int func_id, qp_func_cb cb, void* user,
                          int n_leja, double radius);
+// One restart of newton! on the host, in two parts (the caller times them apart).  Hess: extended Hessenberg matrix, (m + 1) x m,
+// leading dimension ldh; a[0, m), leja[0, m): the Newton coefficients and Leja points of THIS restart.  P, R, Rn: the caller's
+// work vectors (resized to m + 1; a step allocates nothing after its first restart).
+// newton_restart_poly: P[0, m) = coefficients of the Newton polynomial's value in the Krylov basis (src/newton.jl:328-343).
+// newton_restart_next: R[0, m] = coefficients of the next restart's normalised start vector, its norm before that is returned
+// (:356-367); nu != NULL: norms of the stored basis vectors, P and R are converted to that basis (1 / nu_i; 0 where nu_i = 0).
+void newton_restart_poly(const cplx* Hess, int ldh, int m, const cplx* a, const cplx* leja, double radius, double beta,
+                         std::vector<cplx>& P, std::vector<cplx>& R, std::vector<cplx>& Rn);
+double newton_restart_next(const cplx* Hess, int ldh, int m, cplx z_last, double radius, const double* nu, std::vector<cplx>& P,
+                           std::vector<cplx>& R, std::vector<cplx>& Rn);
 int csc_to_csr(int64_t nrows, int64_t ncols, const int64_t* colptr, const int64_t* rowval,
                const qp_c128* nzval, int base, int64_t* rowptr, int32_t* col, qp_c128* vals);
 void partition_rows(const int64_t* rowptr, int64_t nrows, int nparts, int balance, int64_t* bounds);

@@ -424,7 +424,8 @@ def test_partition_rows_property(lens, nparts, balance):
 
 def test_host_numerics_under_sanitizers(tmp_path):
     """The host numerics of the library, compiled with g++ -fsanitize=address,undefined and run on
-    random inputs (tests/sanitize_host_numerics.cpp): no out-of-bounds access, no undefined behaviour."""
+    random inputs (tests/sanitize_host_numerics.cpp): no out-of-bounds access, no undefined behaviour; the host algebra of a
+    newton! restart also bit for bit on named inputs (tests/newton_restart_cases.h)."""
     import shutil
     import subprocess
     if shutil.which("g++") is None:
@@ -441,6 +442,9 @@ def test_host_numerics_under_sanitizers(tmp_path):
     run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
     assert "sanitizer run clean" in run.stdout
+    # one restart of newton! on the host (newton_restart_poly / newton_restart_next) against the table of tests/newton_restart_cases.h
+    named = __import__("re").search(r"newton restart: (\d+) named cases match the table", run.stdout)
+    assert named and int(named.group(1)) >= 12, run.stdout[-2000:]
 
 
 def test_host_index_work_under_sanitizers(tmp_path):
