@@ -499,7 +499,10 @@ int qp_hessenberg_eigvals(const qp_c128* Hess, int ldh, int m, int accumulate, q
  *                          256 partial sums of |q_{j+1}|^2 over the local rows
  *   [all-reduce norm_partials]
  *   qp_krylov_normalize -> h = sqrt(sum), hess_norm[0] = (dt h, 0), hess_norm[1] = (h, 0),
- *                          q_{j+1} *= 1/h unless h < norm_min. */
+ *                          q_{j+1} *= 1/h unless h < norm_min.
+ * qp_krylov_project also records the Gram row <q_j|q_k>, k < j, that its solve formed: a basis whose columns
+ * 0 .. j all went through these building blocks continues in the low-synchronisation form when qp_arnoldi_extend
+ * adds column j + 1 on one GPU (any other basis continues with sequential Gram-Schmidt passes). */
 int qp_krylov_vec(qp_krylov* q, int i, qp_state** out);   /* non-owning view of Arnoldi vector i */
 int qp_krylov_multidot(qp_krylov* q, int j, qp_state* reduced);
 int qp_krylov_project(qp_krylov* q, int j, double dt, const qp_state* reduced, qp_state* hess_col,

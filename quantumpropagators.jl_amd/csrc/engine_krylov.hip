@@ -587,8 +587,11 @@ int qp_krylov_project(qp_krylov* q, int j, double dt, const qp_state* reduced, q
       hess_col->n < j + 1 || norm_partials->n < kRedBlocks)
     return qp::fail(QP_E_BAD_ARG, "qp_krylov_project: bad arguments");
   QP_CHECK(use(q->ctx));
-  return qp::launch_mgs_project(q->ctx->stream, q->Q, q->n, j, q->q(j + 1), reduced->d, q->gram, q->nvec, hess_col->d,
-                                q->mgs_coef, norm_partials->d, dt, q->n, &q->ctx->stats);
+  QP_CHECK(qp::launch_mgs_project(q->ctx->stream, q->Q, q->n, j, q->q(j + 1), reduced->d, q->gram, q->nvec, hess_col->d,
+                                  q->mgs_coef, norm_partials->d, dt, q->n, &q->ctx->stats));
+  // the solve has stored Gram row j: a basis whose columns 0 .. j all came this way continues in the low-synchronisation form
+  if (q->gram_rows >= j) q->gram_rows = j + 1;
+  return QP_OK;
   QP_CATCH
 }
 
