@@ -140,6 +140,12 @@ int qp_csc_to_csr_host(int64_t nrows, int64_t ncols, const int64_t* colptr,
 int qp_partition_rows_host(const int64_t* rowptr, int64_t nrows, int nparts, int balance,
                            int64_t* bounds_out /* nparts+1 */);
 
+/* Which instance of the persistent single-workgroup kernels (small systems: the whole time grid of qp_propagate, a whole Arnoldi
+ * sweep, as ONE launch with the matrix in registers and the vectors in LDS) a system of `n` rows whose longest row has `maxrow`
+ * entries takes when a lane has `max_slots` register slots (16; 32 for the packed / Arnoldi forms): out = {1 if there is one,
+ * lanes per row, entries per lane per row, rows per lane group}; zeros when the system does not fit. */
+int qp_small_plan_host(int64_t n, int64_t maxrow, int max_slots, int64_t out[4]);
+
 /* The index work of the lattice completion (see qp_operator_fill_info) on a host CSR pattern, without a device:
  * rowptr / col of an nrows x ncols pattern with sorted, unique columns; `min_blocks` = the smallest operator (in 64-row
  * blocks) that is completed (the walk_min_blocks knob of a context).  Writes the completed pattern -- the input itself
@@ -221,6 +227,12 @@ int qp_operator_walk_info(const qp_operator* op, int64_t out[8]);
  * wavefront (each wavefront runs in 2 K steps before its first), out[7] = wavefronts per strip column.  Same results bit for bit
  * either way. */
 int qp_operator_walk2_info(const qp_operator* op, int64_t out[8]);
+/* Does this operator take the persistent single-workgroup kernel under the context's knobs (small_nnz), and which instance
+ * (qp_small_plan_host)?  kind 0: the Chebychev time grid of qp_propagate (method 0, at least one step; `m` is ignored); kind 1:
+ * an Arnoldi sweep of `m` columns (qp_arnoldi, and every sweep of qp_newton_step / qp_ritzvals / qp_specrange_arnoldi) -- the
+ * basis of m + 1 vectors and a work vector must fit the LDS.  out = {1 if taken, lanes per row, entries per lane per row, rows
+ * per lane group}; zeros when the general (launch per kernel) path runs.  The same decision the engine takes, not a copy. */
+int qp_operator_small_plan(const qp_operator* op, int kind, int m, int64_t out[4]);
 /* *glong = the long distance L (rows) of a walk plan with one further pair of distances +-L beyond its far reach
  * (a three-dimensional grid's plane distance; its operands are loaded directly), 0 if the plan has none / there is no plan */
 int qp_operator_walk_long(const qp_operator* op, int64_t* glong);

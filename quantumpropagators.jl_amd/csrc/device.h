@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "layout_constants.h"
+#include "small_plan.h"
 #include "walk_geometry.h"
 
 namespace qp {
@@ -353,7 +354,7 @@ struct SmallObs {
 };
 struct SmallArgs {
   int64_t n = 0, nnz = 0;
-  int lanes = 1;                       // lanes per row (power of two <= 64)
+  int lanes = 1;                       // the SmallPlan (small_plan.h): lanes per row (power of two <= 64)
   int ent = 1;                         // entries per lane per row
   int rows_per_group = 1;              // rows per lane group;  rows_per_group * ent <= kSmallEpt
   int obs_lanes = 1;                   // lanes per row for the observables
@@ -379,10 +380,7 @@ struct SmallArgs {
   double limit = 0.0;
   int* fail = nullptr;                 // {flag, step, term}
 };
-constexpr int kSmallThreads = 512;
-constexpr int kSmallEpt = 16;          // register slots per lane of the persistent Chebychev kernel
-constexpr int kSmallEptArnoldi = 32;   // ... of the persistent Arnoldi kernel (fewer live values per slot)
-constexpr int64_t kSmallLdsRows = 2048;
+// (kSmallThreads, the slot counts and the plan itself -- which instance a system takes -- are in small_plan.h)
 // arnoldi! (src/arnoldi.jl:74-100) for a register-resident operator: all m columns in one
 // single-workgroup launch, Krylov basis in LDS (and written to Q for the caller)
 struct SmallArnoldiArgs {
@@ -400,12 +398,8 @@ struct SmallArnoldiArgs {
   double dt = 1.0, norm_min = 0.0;
   int normalize_start = 0;             // q_0 = start / |start|, |start| -> norms[ldd - 1]
 };
-constexpr size_t kSmallLdsBytes = 152 * 1024;
-inline bool small_arnoldi_fits(int64_t n, int m) {
-  return sizeof(double2) * ((size_t)kSmallThreads / 64 + (size_t)(m + 2) * (size_t)n) <= kSmallLdsBytes;
-}
+static_assert(sizeof(double2) == 16, "small_arnoldi_fits (small_plan.h) counts 16 bytes per LDS element");
 int launch_arnoldi_small(hipStream_t s, const SmallArnoldiArgs& a, Stats* st);
-bool small_plan(int64_t n, int64_t maxrow, SmallArgs* a, int max_slots = kSmallEpt);
 int launch_cheby_propagate_small(hipStream_t s, const SmallArgs& a, Stats* st);
 
 int launch_gather_csr_vals(hipStream_t s, double2* out, const double2* vals, const int64_t* map, int64_t nnz,

@@ -193,6 +193,7 @@ struct qp_cheby {
   double* chk_part = nullptr;  // per-workgroup triples (allocated on demand)
   double* chk_out = nullptr;   // per-term triples
   int chk_wg = 0, chk_terms = 0;
+  int bad_term = 0;            // the term whose normalization check failed in the latest step that reported one
   // hipGraph of one step's launches: replayed while the key (everything a launch argument
   // is derived from) stays the same, rebuilt when it changes
   struct GraphKey {
@@ -298,6 +299,15 @@ int operator_csr_mirror(qp_operator* op, bool gather = true);
 // row order in which the batched (SpMM) kernel visits the rows for a panel of `batch` states
 int operator_spmm_order(qp_operator* op, int batch, const int32_t** order_out);
 int operator_spmm_tiles(qp_operator* op, const qp::SpmmTiles** out);
+// ---- the gates of the persistent small-system kernels (kernels_small.hip; the plan itself: small_plan.h) ----
+// longest row of the union pattern
+inline int64_t operator_longest_row(const qp_operator* op) {
+  int64_t maxrow = 0;
+  for (int64_t r = 0; r < op->A.nrows; ++r) maxrow = std::max<int64_t>(maxrow, op->u_rowptr[r + 1] - op->u_rowptr[r]);
+  return maxrow;
+}
+bool cheby_small_fits(const qp_operator* op, qp::SmallPlan* plan);                    // engine_cheby.hip: qp_propagate, method 0
+bool small_sweep_fits(const qp_operator* op, int64_t n, int m, qp::SmallPlan* plan);   // engine_krylov.hip: every arnoldi! of m columns
 // which terms of a cheby! touch the Psi accumulator (include/qprop.h, qp_acc_defer)
 void acc_schedule(const double* a, int n_coeffs, bool defer, qp_acc_defer* out);
 void set_defer(qp::ChebyEpi& e, const qp_acc_defer* d);

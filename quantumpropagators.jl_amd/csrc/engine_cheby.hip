@@ -188,6 +188,20 @@ static int cheby_step_launches(qp_cheby* w, qp_operator* op, qp_state* psi, cons
   return QP_OK;
 }
 
+// does the persistent small-system kernel take a Chebychev time grid of this operator, and with which plan?  (Also behind
+// qp_operator_small_plan.)
+bool cheby_small_fits(const qp_operator* op, qp::SmallPlan* plan) {
+  const qp_ctx* ctx = op->ctx;
+  if (!(ctx->tun.small_nnz > 0 && op->A.nnz <= 2 * (int64_t)ctx->tun.small_nnz && op->nops <= 64)) return false;
+  const int64_t n = op->A.nrows;
+  const int64_t maxrow = operator_longest_row(op);
+  // 16 register slots per lane where that is enough; otherwise 32 (the upper 16 values of a lane
+  // live in LDS: 128 KB, which leaves room for vectors of up to 600 rows)
+  bool ok = op->A.nnz <= ctx->tun.small_nnz && qp::small_plan(n, maxrow, plan, qp::kSmallEpt);
+  if (!ok && n <= 600) ok = qp::small_plan(n, maxrow, plan, 2 * qp::kSmallEpt);
+  return ok;
+}
+
 extern "C" {
 
 // ---------------------------------------------------------------------------
@@ -260,6 +274,19 @@ int qp_operator_walk2_info(const qp_operator* op, int64_t out[8]) {
   out[5] = C.G.S2;
   out[6] = C.G.L;
   out[7] = C.G.nseg;
+  return QP_OK;
+  QP_CATCH
+}
+
+int qp_operator_small_plan(const qp_operator* op, int kind, int m, int64_t out[4]) {
+  QP_TRY
+  if (!op || !out || (kind != 0 && kind != 1) || (kind == 1 && m < 1)) return qp::fail(QP_E_BAD_ARG, "qp_operator_small_plan: bad arguments");
+  qp::SmallPlan p;
+  const bool taken = kind == 0 ? cheby_small_fits(op, &p) : small_sweep_fits(op, op->A.nrows, m, &p);
+  out[0] = taken ? 1 : 0;
+  out[1] = taken ? p.lanes : 0;
+  out[2] = taken ? p.ent : 0;
+  out[3] = taken ? p.rows_per_group : 0;
   return QP_OK;
   QP_CATCH
 }
@@ -382,8 +409,10 @@ int qp_cheby_step(qp_cheby* w, qp_operator* op, qp_state* psi, const double* a, 
     for (int m = 2; m <= nterms; ++m) {
       const double* t = &h[3 * (m - 1)];
       const double map_norm = std::hypot(t[0], t[1]) / (2 * t[2]);   // :195
-      if (!(map_norm <= 1.0 + limit))
-        return qp::fail(QP_E_NORMALIZATION, "Incorrect normalization (E_min=%g, Delta=%g)", E_min, Delta);
+      if (!(map_norm <= 1.0 + limit)) {
+        w->bad_term = m + 1;   // (coefficient a[m + 1] of the reference's 1-based list)
+        return qp::fail(QP_E_NORMALIZATION, "Incorrect normalization (E_min=%g, Delta=%g) in term %d", E_min, Delta, m + 1);
+      }
     }
   }
   return QP_OK;
@@ -656,7 +685,7 @@ int qp_cheby_term_split(qp_operator* op, qp_split* sp, void* boundary_stream, in
 // ---------------------------------------------------------------------------
 // Small systems: the whole time grid in one persistent single-workgroup launch
 // (kernels_small.hip: cheby_propagate_small_kernel).  Same arguments as qp_propagate, method 0.
-static int propagate_cheby_small(qp_operator* op, qp_state* psi, const qp_prop_spec* spec, qp::SmallArgs a,
+static int propagate_cheby_small(qp_operator* op, qp_state* psi, const qp_prop_spec* spec, const qp::SmallPlan& plan,
                                  const double* dts,
                                  const qp_c128* coeff_table, int ncoeffs, int nsteps, qp_operator* const* observables,
                                  int nobs, qp_c128* expvals_out, qp_c128* states_out) {
@@ -677,8 +706,13 @@ static int propagate_cheby_small(qp_operator* op, qp_state* psi, const qp_prop_s
   for (int o = 0; o < nobs; ++o) QP_CHECK(operator_csr_mirror(observables[o]));
   const ChebyScalars sc(spec->Delta, spec->E_min, dts[0]);
 
+  qp::SmallArgs a;
   a.n = n;
   a.nnz = op->A.nnz;
+  a.lanes = plan.lanes;
+  a.ent = plan.ent;
+  a.rows_per_group = plan.rows_per_group;
+  a.obs_lanes = plan.obs_lanes;
   a.rowptr = op->m_rowptr;
   a.cols = op->m_cols;
   a.map = op->m_map;
@@ -763,15 +797,9 @@ int qp_propagate(qp_operator* op, qp_state* psi, const qp_prop_spec* spec, const
   QP_CHECK(use(ctx));
   const int64_t n = psi->n;
   const size_t rows = (size_t)nsteps + 1;
-  if (spec->method == 0 && nsteps > 0 && ctx->tun.small_nnz > 0 && op->A.nnz <= 2 * (int64_t)ctx->tun.small_nnz && op->nops <= 64) {
-    qp::SmallArgs plan;
-    int64_t maxrow = 0;
-    for (int64_t r = 0; r < n; ++r) maxrow = std::max<int64_t>(maxrow, op->u_rowptr[r + 1] - op->u_rowptr[r]);
-    // 16 register slots per lane where that is enough; otherwise 32 (the upper 16 values of a lane
-    // live in LDS: 128 KB, which leaves room for vectors of up to 600 rows)
-    bool ok = op->A.nnz <= ctx->tun.small_nnz && qp::small_plan(n, maxrow, &plan, qp::kSmallEpt);
-    if (!ok && n <= 600) ok = qp::small_plan(n, maxrow, &plan, 2 * qp::kSmallEpt);
-    if (ok)
+  if (spec->method == 0 && nsteps > 0) {
+    qp::SmallPlan plan;
+    if (cheby_small_fits(op, &plan))
       return propagate_cheby_small(op, psi, spec, plan, dts, coeff_table, ncoeffs, nsteps, observables, nobs,
                                    expvals_out, states_out);
   }
@@ -810,8 +838,12 @@ int qp_propagate(qp_operator* op, qp_state* psi, const qp_prop_spec* spec, const
   for (int k = 0; k < nsteps; ++k) {
     if (ncoeffs > 0) QP_CHECK(qp_operator_set_coeffs(op, coeff_table + (size_t)k * ncoeffs, ncoeffs));
     if (spec->method == 0) {
-      QP_CHECK(qp_cheby_step(spec->cheby, op, psi, spec->a, spec->n_coeffs, spec->Delta, spec->E_min, dts[k],
-                             spec->wrk_dt, spec->limit, spec->check_normalization));
+      const int rc = qp_cheby_step(spec->cheby, op, psi, spec->a, spec->n_coeffs, spec->Delta, spec->E_min, dts[k],
+                                   spec->wrk_dt, spec->limit, spec->check_normalization);
+      if (rc == QP_E_NORMALIZATION)   // name the step as well, in the words of the persistent kernel's report (propagate_cheby_small)
+        return qp::fail(rc, "Incorrect normalization (E_min=%g, Delta=%g) in step %d, term %d", spec->E_min, spec->Delta, k + 1,
+                        spec->cheby->bad_term);
+      QP_CHECK(rc);
     } else {
       QP_CHECK(qp_newton_step(spec->newton, op, psi, dts[k], spec->func_id, spec->cb, spec->user, spec->norm_min,
                               spec->relerr, spec->max_restarts, nullptr));

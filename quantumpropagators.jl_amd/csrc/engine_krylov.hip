@@ -304,22 +304,9 @@ int collect_columns(qp_krylov* q, int m, const SweepShape& sw, double norm_min, 
 
 // ---- the three ways to enqueue a sweep ----
 
-// does the persistent small-system kernel take this operator, and with which plan?
-bool small_sweep_fits(const qp_operator* op, const qp_krylov* q, int m, qp::SmallArgs* plan) {
-  const qp_ctx* ctx = op->ctx;
-  if (!(ctx->tun.small_nnz > 0 && op->A.nnz <= (int64_t)ctx->tun.small_nnz * (qp::kSmallEptArnoldi / qp::kSmallEpt) &&
-        qp::small_arnoldi_fits(q->n, m)))
-    return false;
-  int64_t maxrow = 0;
-  for (int64_t r = 0; r < q->n; ++r) maxrow = std::max<int64_t>(maxrow, op->u_rowptr[r + 1] - op->u_rowptr[r]);
-  // the plan of the 16-slot kernels where it exists (same lanes per row, hence the same rounding, as
-  // before the 32-slot variants were added), the larger one only for systems that need it
-  return qp::small_plan(q->n, maxrow, plan, qp::kSmallEpt) || qp::small_plan(q->n, maxrow, plan, qp::kSmallEptArnoldi);
-}
-
 // all m columns in one persistent single-workgroup launch (kernels_small.hip: arnoldi_small_kernel), then one download of the
 // Hessenberg matrix and the norms into pinned memory; |psi| (normalize_start) arrives in norms slot ldd - 1, which is never a column's
-int enqueue_small_sweep(qp_operator* op, qp_krylov* q, const qp::SmallArgs& plan, int m, const qp_state* psi, double dt, int extended,
+int enqueue_small_sweep(qp_operator* op, qp_krylov* q, const qp::SmallPlan& plan, int m, const qp_state* psi, double dt, int extended,
                         double norm_min, bool normalize_start) {
   qp_ctx* ctx = op->ctx;
   const int ldd = q->nvec;
@@ -478,9 +465,9 @@ enum class Sweep { small, onepass, multilaunch };
 // small plan fits -> small; else one-pass wanted, allowed and fits -> one-pass; else multi-launch.  Allowed: only an extended
 // low-synchronisation sweep for a caller that divides its combination coefficients by the stored vectors' norms (newton!).
 // Wanted: by the knob, or by size -- basis + matrix beyond the Infinity Cache.
-Sweep choose_sweep(const qp_operator* op, const qp_krylov* q, int m, bool extended, bool scaled_basis_ok, qp::SmallArgs* plan) {
+Sweep choose_sweep(const qp_operator* op, const qp_krylov* q, int m, bool extended, bool scaled_basis_ok, qp::SmallPlan* plan) {
   const qp_ctx* ctx = op->ctx;
-  if (small_sweep_fits(op, q, m, plan)) return Sweep::small;
+  if (small_sweep_fits(op, q->n, m, plan)) return Sweep::small;
   const double sweep_bytes = 16.0 * (double)q->n * (m + 3) + (op->A.vals_r ? 12.0 : 20.0) * (double)op->A.stored;
   const bool wanted = ctx->tun.arnoldi_onepass >= 2 || (ctx->tun.arnoldi_onepass == 1 && sweep_bytes > 224.0 * 1024 * 1024);
   const bool allowed = extended && scaled_basis_ok && ctx->tun.arnoldi_mode == 1;
@@ -489,6 +476,19 @@ Sweep choose_sweep(const qp_operator* op, const qp_krylov* q, int m, bool extend
 }
 
 }  // namespace
+
+// does the persistent small-system kernel take an Arnoldi sweep of m columns on this operator (n rows), and with which plan?
+// (Also behind qp_operator_small_plan.)
+bool small_sweep_fits(const qp_operator* op, int64_t n, int m, qp::SmallPlan* plan) {
+  const qp_ctx* ctx = op->ctx;
+  if (!(ctx->tun.small_nnz > 0 && op->A.nnz <= (int64_t)ctx->tun.small_nnz * (qp::kSmallEptArnoldi / qp::kSmallEpt) &&
+        n == op->A.nrows && qp::small_arnoldi_fits(n, m)))
+    return false;
+  const int64_t maxrow = operator_longest_row(op);
+  // the plan of the 16-slot kernels where it exists (same lanes per row, hence the same rounding, as
+  // before the 32-slot variants were added), the larger one only for systems that need it
+  return qp::small_plan(n, maxrow, plan, qp::kSmallEpt) || qp::small_plan(n, maxrow, plan, qp::kSmallEptArnoldi);
+}
 
 static int arnoldi_impl(qp_operator* op, qp_krylov* q, int m, const qp_state* psi, double dt, int extended,
                         double norm_min, qp_c128* Hess, int ldh, int* m_out, double* beta_out,
@@ -501,7 +501,7 @@ static int arnoldi_impl(qp_operator* op, qp_krylov* q, int m, const qp_state* ps
   QP_CHECK(use(op->ctx));
   std::memset(Hess, 0, sizeof(qp_c128) * (size_t)ldh * ldh);                                      // :78
   q->nu_valid = false;   // (true only after a one-pass sweep that stands)
-  qp::SmallArgs plan;
+  qp::SmallPlan plan;
   Sweep sweep = choose_sweep(op, q, m, extended != 0, scaled_basis_ok, &plan);
   if (sweep == Sweep::onepass) {
     QP_CHECK(onepass_sweep(op, q, m, psi, dt, norm_min, Hess, ldh, m_out, beta_out, on_column));

@@ -410,32 +410,6 @@ int launch_arnoldi_small(hipStream_t s, const SmallArnoldiArgs& a, Stats* st) {
   return QP_OK;
 }
 
-static_assert(kSmallThreads * kSmallEpt == 8192, "Tuning::small_nnz default = one register slot set (x2 for the 32-slot variants)");
-
-// lanes per row, entries per lane and rows per lane group such that the whole matrix is
-// register-resident; false when the system does not fit (the caller then runs the general loop)
-bool small_plan(int64_t n, int64_t maxrow, SmallArgs* a, int max_slots) {
-  if (n < 1 || n > kSmallLdsRows) return false;
-  for (int t = 1; t <= 64; t <<= 1) {
-    const int64_t ngrp = kSmallThreads / t;
-    const int64_t rows = (n + ngrp - 1) / ngrp;
-    int64_t ent = 1;
-    while (ent * t < maxrow) ent <<= 1;   // compile-time variants: 1, 2, 4, 8, 16 (Arnoldi: also 32)
-    int64_t rows_p2 = 1;
-    while (rows_p2 < rows) rows_p2 <<= 1;
-    if (rows_p2 * ent <= max_slots) {   // smallest t: fewest cross-lane reduction levels
-      a->lanes = t;
-      a->ent = (int)ent;
-      a->rows_per_group = (int)rows_p2;
-      int to = 1;
-      while (to < 64 && (int64_t)kSmallThreads / (2 * to) >= n) to <<= 1;
-      a->obs_lanes = to;
-      return true;
-    }
-  }
-  return false;
-}
-
 int launch_cheby_propagate_small(hipStream_t s, const SmallArgs& a, Stats* st) {
   const int slots = a.ent * a.rows_per_group;
   const size_t lds = sizeof(double2) * (kSmallThreads / 64 + (size_t)a.nops + 3 * (size_t)a.n +

@@ -123,6 +123,7 @@ SIGNATURES = {
     "qp_timer_end": (C.c_int, [_P, _dp]),
     "qp_csc_to_csr_host": (C.c_int, [C.c_int64, C.c_int64, _i64p, _i64p, _cp, C.c_int, _i64p, _i32p, _cp]),
     "qp_partition_rows_host": (C.c_int, [_i64p, C.c_int64, C.c_int, C.c_int, _i64p]),
+    "qp_small_plan_host": (C.c_int, [C.c_int64, C.c_int64, C.c_int, _i64p]),
     "qp_matrix_create": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _i64p, _i64p, _P, C.c_int,
                                    C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "qp_matrix_destroy": (C.c_int, [_P]),
@@ -138,6 +139,7 @@ SIGNATURES = {
     "qp_operator_build_info": (C.c_int, [_P, _dp]),
     "qp_operator_walk_info": (C.c_int, [_P, _i64p]),
     "qp_operator_walk2_info": (C.c_int, [_P, _i64p]),
+    "qp_operator_small_plan": (C.c_int, [_P, C.c_int, C.c_int, _i64p]),
     "qp_operator_fill_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "qp_developer_build": (C.c_int, []),
     "qp_operator_walk_long": (C.c_int, [_P, C.POINTER(C.c_int64)]),
@@ -410,6 +412,15 @@ def partition_rows(rowptr, nparts, balance="rows"):
     return out
 
 
+def small_plan(n, maxrow, max_slots=16):
+    """Instance of the persistent small-system kernels for ``n`` rows with at most ``maxrow`` entries each and ``max_slots``
+    register slots per lane (include/qprop.h: qp_small_plan_host; no device needed): ``(lanes, ent, rows_per_group)``, or
+    ``None`` when the system does not fit."""
+    out = np.zeros(4, dtype=np.int64)
+    check(load().qp_small_plan_host(int(n), int(maxrow), int(max_slots), _ptr(out, _i64p)))
+    return (int(out[1]), int(out[2]), int(out[3])) if out[0] else None
+
+
 # ------------------------------------------------------------------------------
 # handles
 # ------------------------------------------------------------------------------
@@ -576,6 +587,14 @@ class Operator:
         n = C.c_int64(0)
         check(self.lib.qp_operator_fill_info(self._h, C.byref(n)))
         return n.value
+
+    def small_plan(self, kind="cheby", m=1):
+        """Does ``propagate`` (``kind="cheby"``) / an Arnoldi sweep of ``m`` columns (``kind="arnoldi"``) of this operator run as ONE
+        persistent single-workgroup launch, and which kernel instance (include/qprop.h: qp_operator_small_plan)?
+        ``(lanes, ent, rows_per_group)``, or ``None`` when the general path runs."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self.lib.qp_operator_small_plan(self._h, {"cheby": 0, "arnoldi": 1}[kind], int(m), _ptr(out, _i64p)))
+        return (int(out[1]), int(out[2]), int(out[3])) if out[0] else None
 
     def walk2_info(self):
         """Does a whole-operator ``cheby!`` take the two-term strip walk (include/qprop.h: qp_operator_walk2_info)?"""

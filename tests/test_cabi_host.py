@@ -455,7 +455,8 @@ def test_host_index_work_under_sanitizers(tmp_path):
     bounds-checked) and fuzzed over tall / wide / 1-row / N < 64 / empty-row shapes, lattices and spin chains
     (tests/sanitize_host_index.cpp; the 5681 x 358 operator of the round-4 GPU memory fault is the first case).  Every stored slot
     -- pads and the lanes beyond the last row included -- must decode to a column inside the matrix, every pad must be zero.
-    The layout unit (csrc/operator_layout.cpp) and the launch geometry of the strip walks (csrc/walk_geometry.cpp) must stay pure host
+    The layout unit (csrc/operator_layout.cpp), the launch geometry of the strip walks (csrc/walk_geometry.cpp) and the plan of the
+    persistent small-system kernels (csrc/small_plan.cpp) must stay pure host
     code: they compile without the HIP stand-in on the include path.  For every operator with a strip-walk plan the harness sweeps the
     cut of its launches over chip sizes and knobs against the kernels' own segment formulas (every strip step in exactly one
     segment, every edge block reached, the launch fits the chip) and checks a table of named inputs (tests/walk_geometry_cases.h)."""
@@ -465,7 +466,7 @@ def test_host_index_work_under_sanitizers(tmp_path):
         pytest.skip("g++ not available")
     csrc = os.path.join(ROOT, "quantumpropagators.jl_amd", "csrc")
     exe = str(tmp_path / "host_index_san")
-    for unit in ("operator_layout.cpp", "walk_geometry.cpp"):
+    for unit in ("operator_layout.cpp", "walk_geometry.cpp", "small_plan.cpp"):
         pure = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", csrc, os.path.join(csrc, unit)], capture_output=True, text=True)
         assert pure.returncode == 0, pure.stderr[-3000:]
     build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-x", "c++",

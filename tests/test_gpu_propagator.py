@@ -283,12 +283,20 @@ def test_fused_propagate_equals_stepwise(ctx, method, backward):
         P.propagate(psi0, gen, tlist, method=method, ctx=ctx, fused=True, callback=lambda *a: None, **kw)
 
 
+# which instance of the persistent kernel the cases of test_persistent_small_cheby select (None: none -- they fall back)
+_PERSISTENT_SMALL_PLANS = {2: (1, 2, 1), 3: (1, 4, 1), 55: (2, 16, 1), 64: (4, 16, 1), 100: (4, 32, 1), 128: (4, 32, 1),
+                           130: None, 700: None, 2048: None, 3000: None}
+
+
 @pytest.mark.parametrize("N,dense,ncontrols", [(2, True, 1), (3, True, 0), (55, False, 0), (64, True, 2),
                                                (100, True, 1), (128, True, 2), (130, True, 1), (700, False, 2), (2048, False, 1), (3000, False, 1)])
 def test_persistent_small_cheby(ctx, N, dense, ncontrols):
-    """The single-launch time grid for small systems (register-resident rows, LDS vectors,
-    streaming rows, vectors in global memory -- one case each) against the oracle, the
-    general loop, with observables, backward, and the normalization check."""
+    """The single-launch time grid for small systems (the matrix in the lanes' registers, the vectors in LDS) against the oracle,
+    the general loop, with observables, backward, and the normalization check.  N = 2 ... 128 take the persistent kernel -- which
+    instance, by qp_operator_small_plan, and that it ran, by the launch count; N = 130 (16900 entries: more than 2 x small_nnz),
+    700 and 2048 (too many entries as well) and 3000 (more rows than the LDS vectors hold) fall back to the general loop, whose
+    result the same assertions then hold against the oracle (tests/test_gpu_small_instances.py has every other instance)."""
+    plan = _PERSISTENT_SMALL_PLANS[N]
     rng = np.random.default_rng(N)
     if dense:
         mats = [synth.dense_hermitian(N, rho=2.0 if i == 0 else 0.5, rng=rng) for i in range(ncontrols + 1)]
@@ -303,8 +311,13 @@ def test_persistent_small_cheby(ctx, N, dense, ncontrols):
     psi0 = rng.standard_normal(N) + 1j * rng.standard_normal(N)
     psi0 /= np.linalg.norm(psi0)
     kw = dict(E_min=-4.0, E_max=4.0)
+    op = L.Operator(ctx, [L.Matrix.from_scipy(ctx, m) if sp.issparse(m) else L.Matrix.from_dense(ctx, m) for m in mats], ncontrols)
+    assert op.small_plan("cheby") == plan          # (lanes, ent, rows_per_group), None: the general loop
+    op.close()
     for backward in (False, True):
+        ctx.reset_stats()
         out, st = P.propagate(psi0, gen, tlist, method="cheby", storage=True, backward=backward, ctx=ctx, **kw)
+        assert (ctx.stats()["n_kernel_launches"] < nt - 1) == (plan is not None)    # the general loop: a launch per term and step at least
         ref, rst = qo.propagate(psi0, ogen, tlist, "cheby", storage=True, backward=backward, **kw)
         assert np.max(np.linalg.norm(st - rst, axis=0)) < 1e-10 and np.linalg.norm(out - ref) < 1e-10
         L.tuning_set("small_nnz", 0)
