@@ -10,6 +10,7 @@
 #include <rocblas/rocblas.h>
 
 #include "engine.h"
+#include "zgemm_mfma.h"
 
 namespace {
 
@@ -101,16 +102,22 @@ __global__ __launch_bounds__(qp::kThreads) void liouville_combine_kernel(double2
 // ---------------------------------------------------------------------------
 // Hand-written fp64 matrix-core kernel for the sizes where a chain of library GEMMs is bound
 // by its launches (default: n < 260):  Y = beta Y + sum_j alpha_j P_j op_j(Q_j)  in ONE launch, all
-// matrices n x n, column-major.  v_mfma_f64_16x16x4_f64: lane l holds A[l & 15][l >> 4] and
-// B[l >> 4][l & 15]; D register r of lane l is D[(l >> 4) + 4 r][l & 15].  A complex
-// product is four real ones (Re += ar br - ai bi, Im += ar bi + ai br).
-//   * one workgroup = one 16 x 16 tile of Y (BM = 1); its four wavefronts split the inner
+// matrices n x n, column-major.  MFMA lane layout and accumulate: zgemm_mfma.h.
+//   * one workgroup = one 16 x 16 tile of Y; its four wavefronts split the inner
 //     dimension in four and are summed through LDS in wave order (deterministic);
 //   * operands go from L2 straight into registers in the MFMA lane layout (the matrices are at
-//     most 4 MB each), software-pipelined D k-steps ahead across the flattened (term, k) loop;
+//     most 4 MB each), software-pipelined D k-steps ahead across the flattened (term, k) loop --
+//     guarded, per-term loads with alpha_j and the conjugate transpose applied on the way: not the
+//     branch-free pipeline of the 32 x 32 kernel, the launch count decides at these sizes;
 //   * `batched`: workgroup z computes only term z into Y + z n^2 (the K products A_k rho).
 // ---------------------------------------------------------------------------
-typedef double v4d __attribute__((ext_vector_type(4)));
+using qp::dealt_pair;
+using qp::KQuarter;
+using qp::ld_off;
+using qp::TilePair;
+using qp::wave_order_sum;
+using qp::wave_quarter;
+using qp::ZgemmTile;
 constexpr int kMaxTerms = 10;
 struct GemmTerm {
   const double2* P;
@@ -123,73 +130,46 @@ struct GemmTerms {
   int n_terms;
 };
 
-template <int BM, int D>   // D = k-steps of prefetch
+template <int D>   // D = k-steps of prefetch
 __global__ __launch_bounds__(256) void zgemm_sum_kernel(double2* __restrict__ Y, int n, double2 beta, GemmTerms terms,
                                                         int batched) {
-  __shared__ double red[3][BM * BM][2][4][64];   // partial tiles of waves 1..3
+  __shared__ double red[3][2][4][64];   // partial tiles of waves 1..3
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int row0 = blockIdx.x * 16 * BM, col0 = blockIdx.y * 16 * BM;
+  const int row0 = blockIdx.x * 16, col0 = blockIdx.y * 16;
   const int first = batched ? blockIdx.z : 0;
   const int nt = batched ? 1 : terms.n_terms;
   double2* __restrict__ Yz = Y + (batched ? (size_t)blockIdx.z * n * n : 0);
-  // this wave's share of the inner dimension, in k-steps of 4
-  const int ksteps = (n + 3) / 4;
-  const int per = (ksteps + 3) / 4;
-  const int sbeg = wave * per;
-  const int send = min(ksteps, sbeg + per);
-  const int nsteps = max(send - sbeg, 0);
+  // this wave's share of the inner dimension, in k-steps of 4 (the last one masked by the loads)
+  const KQuarter q = wave_quarter((n + 3) / 4, wave);
+  const int sbeg = q.sbeg, nsteps = q.nsteps;
   const int total = nt * nsteps;
   const int li = lane & 15, lk = lane >> 4;
 
-  v4d cr[BM][BM], ci[BM][BM];
-#pragma unroll
-  for (int a = 0; a < BM; ++a)
-#pragma unroll
-    for (int b = 0; b < BM; ++b) cr[a][b] = ci[a][b] = v4d{0.0, 0.0, 0.0, 0.0};
-
-  double2 fa[D][BM], fb[D][BM];
+  ZgemmTile<1, 1> acc;
+  acc.zero();
+  double2 fa[D][1], fb[D][1];
   auto load = [&](int slot, int flat) {
     const int t = first + flat / nsteps;
     const int k = (sbeg + flat % nsteps) * 4 + lk;
     const GemmTerm& tm = terms.t[t];
-    const bool kin = k < n;
-#pragma unroll
-    for (int a = 0; a < BM; ++a) {
-      const int r = row0 + a * 16 + li;
-      const bool ok = kin && r < n;
-      const double2 v = tm.P[ok ? (size_t)k * n + r : 0];
-      fa[slot][a] = ok ? v : make_double2(0.0, 0.0);
+    const int r = row0 + li, c = col0 + li;
+    const bool oka = k < n && r < n, okb = k < n && c < n;
+    const double2 va = tm.P[oka ? (size_t)k * n + r : 0];
+    fa[slot][0] = oka ? va : make_double2(0.0, 0.0);
+    double2 vb;
+    if (tm.conjT) {   // op(Q)[k][c] = conj(Q[c][k])
+      vb = tm.Q[okb ? (size_t)k * n + c : 0];
+      vb.y = -vb.y;
+    } else {
+      vb = tm.Q[okb ? (size_t)c * n + k : 0];
     }
-#pragma unroll
-    for (int b = 0; b < BM; ++b) {
-      const int c = col0 + b * 16 + li;
-      const bool ok = kin && c < n;
-      double2 v;
-      if (tm.conjT) {   // op(Q)[k][c] = conj(Q[c][k])
-        v = tm.Q[ok ? (size_t)k * n + c : 0];
-        v.y = -v.y;
-      } else {
-        v = tm.Q[ok ? (size_t)c * n + k : 0];
-      }
-      fb[slot][b] = ok ? v : make_double2(0.0, 0.0);
-    }
+    fb[slot][0] = okb ? vb : make_double2(0.0, 0.0);
   };
   auto compute = [&](int slot, int flat) {
-    const double2 al = terms.t[first + flat / nsteps].alpha;
-#pragma unroll
-    for (int a = 0; a < BM; ++a) {
-      const double2 x = fa[slot][a];
-      const double ar = al.x * x.x - al.y * x.y, ai = al.x * x.y + al.y * x.x;   // alpha_j folded into the A fragment
-#pragma unroll
-      for (int b = 0; b < BM; ++b) {
-        const double2 y = fb[slot][b];
-        cr[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, y.x, cr[a][b], 0, 0, 0);
-        cr[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(-ai, y.y, cr[a][b], 0, 0, 0);
-        ci[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, y.y, ci[a][b], 0, 0, 0);
-        ci[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, y.x, ci[a][b], 0, 0, 0);
-      }
-    }
+    const double2 al = terms.t[first + flat / nsteps].alpha, x = fa[slot][0];
+    const double2 ax[1] = {make_double2(al.x * x.x - al.y * x.y, al.x * x.y + al.y * x.x)};   // alpha_j folded into the A fragment
+    acc.template step<true>(ax, fb[slot]);
   };
 #pragma unroll
   for (int d = 0; d < D; ++d)
@@ -203,69 +183,50 @@ __global__ __launch_bounds__(256) void zgemm_sum_kernel(double2* __restrict__ Y,
       }
     }
   }
-  // sum the four k-quarters in wave order
+  // sum the four k-quarters in wave order (wavefront 0 adds the others' to its registers: 12 KB of LDS, not 16)
   if (wave > 0) {
 #pragma unroll
-    for (int a = 0; a < BM; ++a)
-#pragma unroll
-      for (int b = 0; b < BM; ++b)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          red[wave - 1][a * BM + b][0][r][lane] = cr[a][b][r];
-          red[wave - 1][a * BM + b][1][r][lane] = ci[a][b][r];
-        }
+    for (int r = 0; r < 4; ++r) {
+      red[wave - 1][0][r][lane] = acc.cr[0][0][r];
+      red[wave - 1][1][r][lane] = acc.ci[0][0][r];
+    }
   }
   __syncthreads();
   if (wave == 0) {
     const bool bz = (beta.x == 0.0 && beta.y == 0.0) || batched;
 #pragma unroll
-    for (int a = 0; a < BM; ++a)
-#pragma unroll
-      for (int b = 0; b < BM; ++b)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          double vr = cr[a][b][r], vi = ci[a][b][r];
-          for (int w = 0; w < 3; ++w) {
-            vr += red[w][a * BM + b][0][r][lane];
-            vi += red[w][a * BM + b][1][r][lane];
-          }
-          const int row = row0 + a * 16 + lk + 4 * r, col = col0 + b * 16 + li;
-          if (row < n && col < n) {
-            double2* y = Yz + (size_t)col * n + row;
-            if (!bz) {
-              const double2 o = *y;
-              vr += beta.x * o.x - beta.y * o.y;
-              vi += beta.x * o.y + beta.y * o.x;
-            }
-            *y = make_double2(vr, vi);
-          }
+    for (int r = 0; r < 4; ++r) {
+      double vr = acc.cr[0][0][r], vi = acc.ci[0][0][r];
+      for (int w = 0; w < 3; ++w) {
+        vr += red[w][0][r][lane];
+        vi += red[w][1][r][lane];
+      }
+      const int row = row0 + lk + 4 * r, col = col0 + li;
+      if (row < n && col < n) {
+        double2* y = Yz + (size_t)col * n + row;
+        if (!bz) {
+          const double2 o = *y;
+          vr += beta.x * o.x - beta.y * o.y;
+          vi += beta.x * o.y + beta.y * o.x;
         }
+        *y = make_double2(vr, vi);
+      }
+    }
   }
 }
 
 // ---------------------------------------------------------------------------
 // The sum of products for the sizes above (default 260 <= n <= 2048: knobs liouville_tile32_min_n, liouville_tile32_n):
 //   Y = beta Y + alpha sum_j P_j Q_j      (`batched`: Y_z = alpha P_z Q_z for every z)
-// On MI355X the fp64 MFMA runs at the rate of the fp64 vector unit and shares its issue: every vector-ALU
-// instruction between two MFMAs is time the matrix pipe stands still, from the same or from another wavefront
-// (tools/probe/mfma_f64_rate.hip: 27.2 ns per v_mfma_f64_16x16x4_f64 and SIMD with none, 31.8 with two, 38.0 with six).
-// So the k loop of this kernel has next to no vector-ALU work in it:
-//   * one workgroup = one 32 x 32 tile of Y; each of its four wavefronts owns a quarter of the inner dimension of
-//     every product and keeps the whole tile -- 2 x 2 MFMA tiles, real and imaginary part, 64 accumulator
-//     registers (VGPR form: -mllvm -amdgpu-mfma-vgpr-form, no AGPR copies) -- so a k-step of 4 is four 1-KiB
-//     loads for 16 MFMAs (16 B per clock and CU from L2; 16 x 16 tiles need twice that and run into the L2 -> CU rate);
+// on the shared tile core (zgemm_mfma.h: the lane layout, the measured rule that keeps vector-ALU work out of the k loop, the
+// pipelined k loop, the wave-order sum).  What is this kernel's own:
+//   * one workgroup = one 32 x 32 tile of Y: 2 x 2 MFMA tiles, 64 accumulator registers per wavefront, so a k-step of 4 is
+//     four 1-KiB loads for 16 MFMAs (16 B per clock and CU from L2; 16 x 16 tiles need twice that and run into the L2 -> CU rate);
 //   * the operands go from the loaded registers into the MFMAs as they are: every product has coefficient one and
 //     no conjugation -- the caller stores -M_R and the conjugate-transposed Lindblad operators once, the factor of
-//     the dissipator is applied to T_k = A_k rho by the first launch's epilogue, alpha and beta by the second's --
-//     and the only vector-ALU instructions per k-step are the sign flips of the two imaginary A fragments;
-//   * addresses are a scalar base per operand, advanced by the scalar unit, plus a per-lane offset that never
-//     changes (buffer loads); the cursors over the flattened (product, k) range advance by scalar selects,
-//     not branches, so that a k-step stays one basic block and its four refills and scalar work are spread between
-//     the MFMAs (sched_group_barrier);
-//   * software pipeline of D slots: step g runs on slot g mod D while the slot of step g - 1 is refilled for step
-//     g - 1 + D; no conditions between the first load and the last refill of the steady state (the compiler's
-//     vmcnt values are exact only along an unconditional path).
-// The four partial tiles are summed through LDS in wave order, as in the 16 x 16 kernel: deterministic.
+//     the dissipator is applied to T_k = A_k rho by the first launch's epilogue, alpha and beta by the second's;
+//   * the k loop runs over the flattened (product, k) range of this wavefront's quarter: its cursors advance by scalar
+//     selects, not branches, so that a k-step stays one basic block.
 // ---------------------------------------------------------------------------
 struct Gemm32Terms {
   const double2* P[kMaxTerms];
@@ -273,15 +234,10 @@ struct Gemm32Terms {
   int n_terms;
 };
 
-// 16 bytes at (wave-uniform base) + (32-bit lane offset): a buffer load, whose descriptor the scalar unit builds from
-// the base -- no vector-ALU address arithmetic
-typedef unsigned u4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ double2 ld_off(const double2* base, unsigned off) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<double2*>(base), (short)0, -1, 0x00020000);
-  const u4v v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-  double2 d;
-  __builtin_memcpy(&d, &v, 16);
-  return d;
+// a b with the fused multiply-adds written out: a.y b.y and a.x b.y are rounded on their own, a.x b.x and a.y b.x go into the
+// fma.  -ffp-contract may fuse either product of each pair; this choice is the one tests/test_gpu_zgemm_bits.py pins.
+__device__ __forceinline__ double2 cmul_pinned(double2 a, double2 b) {
+  return make_double2(fma(a.x, b.x, -(a.y * b.y)), fma(a.y, b.x, a.x * b.y));
 }
 
 template <int D>
@@ -296,25 +252,19 @@ __global__ __launch_bounds__(256) void zgemm_sum32_kernel(double2* __restrict__ 
   const int tlast = first + nt - 1;
   double2* __restrict__ Yz = Y + (batched ? (size_t)blockIdx.z * n * n : 0);
   const int ksteps = n >> 2;   // whole k-steps; the n & 3 inner indices left over: one masked step after the loop
-  const int per = (ksteps + 3) / 4;
-  const int sbeg = wave * per;
-  const int nsteps = max(min(ksteps, sbeg + per) - sbeg, 0);
-  const int total = nt * nsteps;
+  const KQuarter q = wave_quarter(ksteps, wave);
+  const int nsteps = q.nsteps;
   const int li = lane & 15, lk = lane >> 4;
   const int ra0 = min(row0 + li, n - 1), ra1 = min(row0 + 16 + li, n - 1);
   const int cb0 = min(col0 + li, n - 1), cb1 = min(col0 + 16 + li, n - 1);
   // A fragment: P[r + k n], k = 4 step + lk;  B fragment: Q[k + c n]
   const unsigned oa0 = (unsigned)(lk * n + ra0) * 16u, oa1 = (unsigned)(lk * n + ra1) * 16u;
   const unsigned ob0 = (unsigned)(cb0 * n + lk) * 16u, ob1 = (unsigned)(cb1 * n + lk) * 16u;
-  const size_t startA = (size_t)sbeg * 4 * n, startB = (size_t)sbeg * 4;   // this wave's first k, in elements
+  const size_t startA = (size_t)q.sbeg * 4 * n, startB = (size_t)q.sbeg * 4;   // this wave's first k, in elements
   const size_t strideA = (size_t)4 * n, strideB = 4;
 
-  v4d cr[2][2], ci[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) cr[a][b] = ci[a][b] = v4d{0.0, 0.0, 0.0, 0.0};
-
+  ZgemmTile<2, 2> acc;
+  acc.zero();
   double2 fa[D][2], fb[D][2];
   int lt = first, ls = 0;   // refill cursor: product, k-step
   const double2* baseA = terms.P[first] + startA;
@@ -338,71 +288,8 @@ __global__ __launch_bounds__(256) void zgemm_sum32_kernel(double2* __restrict__ 
     nextA = terms.P[lt2] + startA;
     nextB = terms.Q[lt2] + startB;
   };
-  auto mfma = [&](int slot) {   // 16 MFMAs; consecutive ones never share an accumulator
-    double nai[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) nai[a] = -fa[slot][a].y;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        cr[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[slot][a].x, fb[slot][b].x, cr[a][b], 0, 0, 0);
-        ci[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[slot][a].x, fb[slot][b].y, ci[a][b], 0, 0, 0);
-      }
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        cr[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(nai[a], fb[slot][b].y, cr[a][b], 0, 0, 0);
-        ci[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[slot][a].y, fb[slot][b].x, ci[a][b], 0, 0, 0);
-      }
-  };
-  int s = 0;
-  if (total >= 2 * D - 1) {
-#pragma unroll
-    for (int d = 0; d < D - 1; ++d) {
-      load(d);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    for (; s + 2 * D - 1 <= total; s += D) {
-#pragma unroll
-      for (int j = 0; j < D; ++j) {
-        load((j + D - 1) % D);
-        mfma(j);
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                 // one MFMA
-          __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);                 // at most one vector-ALU instruction
-          __builtin_amdgcn_sched_group_barrier(0x004, 2, 0);                 // scalar work of the cursor
-          if (g % 4 == 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // one of the four refills
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    // here steps s .. s + D - 2 are loaded or in flight, in slots 0 .. D - 2
-    for (; s < total; s += D) {
-#pragma unroll
-      for (int j = 0; j < D; ++j) {
-        if (s + j < total) {
-          if (s + j + D - 1 < total) load((j + D - 1) % D);
-          mfma(j);
-        }
-      }
-    }
-  } else {
-#pragma unroll
-    for (int d = 0; d < D; ++d)
-      if (d < total) load(d);
-    for (; s < total; s += D) {
-#pragma unroll
-      for (int d = 0; d < D; ++d) {
-        if (s + d < total) {
-          mfma(d);
-          if (s + d + D < total) load(d);
-        }
-      }
-    }
-  }
+  auto step = [&](int slot) { acc.template step<true>(fa[slot], fb[slot]); };
+  qp::pipelined_ksteps<D, 16, 4, 1>(nt * nsteps, load, step);   // a refill behind the second of every four MFMAs
   // n not a multiple of 4: one more k-step per product for the n & 3 inner indices left over, the lanes past the end
   // masked out of the A fragment (products dealt round-robin to the wavefronts; outside the pipelined loop)
   if (n & 3) {
@@ -416,43 +303,26 @@ __global__ __launch_bounds__(256) void zgemm_sum32_kernel(double2* __restrict__ 
       fa[0][1] = kin ? p1 : zero;
       fb[0][0] = terms.Q[t][(size_t)cb0 * n + kc];
       fb[0][1] = terms.Q[t][(size_t)cb1 * n + kc];
-      mfma(0);
+      step(0);
     }
   }
-  // sum the four k-quarters in wave order; every wavefront finishes one of the four 16 x 16 tiles (all four partial
-  // tiles of everybody go through LDS, so that no register is indexed by the wave number)
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        red[wave][a * 2 + b][0][r][lane] = cr[a][b][r];
-        red[wave][a * 2 + b][1][r][lane] = ci[a][b][r];
-      }
+  // every wavefront finishes one of the four 16 x 16 tiles: wavefront w the registers r = 0 .. 3 of MFMA tile w
+  acc.store(red, wave, lane);
   __syncthreads();
-  {
-    const bool bz = (beta.x == 0.0 && beta.y == 0.0) || batched;
-    const int a = wave >> 1, b = wave & 1;
+  const bool bz = (beta.x == 0.0 && beta.y == 0.0) || batched;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      double sr = red[0][wave][0][r][lane], si = red[0][wave][1][r][lane];
-#pragma unroll
-      for (int w = 1; w < 4; ++w) {
-        sr += red[w][wave][0][r][lane];
-        si += red[w][wave][1][r][lane];
+  for (int i = 0; i < 4; ++i) {
+    const TilePair p = dealt_pair<4>(wave, i);
+    const double2 sum = wave_order_sum<4>(red, p, lane);
+    const int row = row0 + (p.tile >> 1) * 16 + lk + 4 * p.r, col = col0 + (p.tile & 1) * 16 + li;
+    if (row < n && col < n) {
+      double2 v = cmul_pinned(alpha, sum);
+      double2* y = Yz + (size_t)col * n + row;
+      if (!bz) {
+        const double2 bo = cmul_pinned(beta, *y);
+        v = make_double2(v.x + bo.x, v.y + bo.y);
       }
-      const int row = row0 + a * 16 + lk + 4 * r, col = col0 + b * 16 + li;
-      if (row < n && col < n) {
-        double vr = alpha.x * sr - alpha.y * si, vi = alpha.x * si + alpha.y * sr;
-        double2* y = Yz + (size_t)col * n + row;
-        if (!bz) {
-          const double2 o = *y;
-          vr += beta.x * o.x - beta.y * o.y;
-          vi += beta.x * o.y + beta.y * o.x;
-        }
-        *y = make_double2(vr, vi);
-      }
+      *y = v;
     }
   }
 }
@@ -462,7 +332,7 @@ int launch_zgemm_sum32(hipStream_t s, double2* Y, int n, double2 alpha, double2 
   if (terms.n_terms == 0) return QP_OK;
   const int tiles = (n + 31) / 32;
   const dim3 grid(tiles, tiles, batched ? terms.n_terms : 1);
-  // six slots: 172 VGPRs, two wavefronts per SIMD; four or five slots (three per SIMD) measured 1-2 % either way up to
+  // six slots: 176 VGPRs, two wavefronts per SIMD; four or five slots (three per SIMD) measured 1-2 % either way up to
   // n = 768 and 15 % slower at n = 1024 (profiles/r02/liouville_paths.txt)
   hipLaunchKernelGGL((zgemm_sum32_kernel<6>), grid, dim3(256), 0, s, Y, n, alpha, beta, terms, batched);
   QP_HIP(hipGetLastError());
@@ -489,7 +359,7 @@ int launch_zgemm_sum(hipStream_t s, double2* Y, int n, double2 beta, const GemmT
   // 16 x 16 tiles: as many workgroups as the matrix offers (small n: the launch count decides)
   const int tiles = (n + 15) / 16;
   const dim3 grid(tiles, tiles, batched ? terms.n_terms : 1);
-  hipLaunchKernelGGL((zgemm_sum_kernel<1, 8>), grid, dim3(256), 0, s, Y, n, beta, terms, batched);
+  hipLaunchKernelGGL((zgemm_sum_kernel<8>), grid, dim3(256), 0, s, Y, n, beta, terms, batched);
   QP_HIP(hipGetLastError());
   if (st) st->n_launch++;
   return QP_OK;

@@ -10,15 +10,14 @@
 //   b states     dense_zgemm_cheby_kernel: Y[N x b] = epilogue(H X) -- here H [psi_1 .. psi_b] IS a dense panel
 //                contraction (the case BASELINE's north_star reserves the matrix cores for): arithmetic intensity b / 2
 //                flop per byte, beyond the fp64 ridge (9.8) from b = 20.  v_mfma_f64_16x16x4_f64, a complex product as four
-//                real MFMAs (two when H is real); the k loop is built like engine_liouville.hip's 32 x 32 kernel, whose
-//                measured rule it follows: on this chip the fp64 MFMA shares the issue of the fp64 vector unit, so the loop
-//                carries no vector-ALU work but two sign flips -- operands go from L2 into the MFMA lane layout through
-//                buffer loads (scalar base advanced by the scalar unit + a constant lane offset), software-pipelined D
-//                deep, and the recurrence + accumulate of the Chebyshev term run in the epilogue of the tile.
+//                real MFMAs (two when H is real) on the tile core of zgemm_mfma.h (lane layout, pipelined k loop and its
+//                measured rule, wave-order sum: described there); the recurrence + accumulate of the Chebyshev term run
+//                in the epilogue of the tile.
 // gfx950 only.  Build with -mllvm -amdgpu-mfma-vgpr-form (accumulators stay in VGPRs across the k loop).
 #include <type_traits>
 
 #include "kernel_common.h"
+#include "zgemm_mfma.h"
 
 namespace qp {
 
@@ -122,40 +121,15 @@ int launch_dense_gemv_plain(hipStream_t s, const DevMatrix& A, const double2* x,
 // ---------------------------------------------------------------------------
 // b states: the fused Chebyshev term of the panel on the fp64 matrix cores
 // ---------------------------------------------------------------------------
-typedef double v4d __attribute__((ext_vector_type(4)));
-typedef unsigned u4v __attribute__((ext_vector_type(4)));
-typedef unsigned u2v __attribute__((ext_vector_type(2)));
-
-// 16 (or 8) bytes at (wave-uniform base) + (32-bit lane offset): a buffer load whose descriptor the scalar unit builds from
-// the base -- no vector-ALU address arithmetic in the k loop
-__device__ __forceinline__ double2 ld_off(const double2* base, unsigned off) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<double2*>(base), (short)0, -1, 0x00020000);
-  const u4v v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-  double2 d;
-  __builtin_memcpy(&d, &v, 16);
-  return d;
-}
-__device__ __forceinline__ double2 ld_off(const double* base, unsigned off) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(base), (short)0, -1, 0x00020000);
-  const u2v v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0);
-  double d;
-  __builtin_memcpy(&d, &v, 8);
-  return make_double2(d, 0.0);
-}
-
-// One workgroup = one (16 TA) x (16 TB) tile of the panel (rows i0 .., states s0 ..); each of its four wavefronts owns a quarter
-// of the inner dimension and keeps the whole tile (TA x TB MFMA tiles, real and imaginary part: 8 TA TB accumulator
-// registers); a k-step of 4 is TA + TB loads for 4 TA TB MFMAs (2 TA TB when H is real).  TA = TB = 2 (32 x 32) for panels of
-// more than 16 states: 16 MFMAs per four 1-KiB loads, the MFMA rate decides (N = 4096, b = 64: 61 TFLOP/s); TA = TB = 1
-// (16 x 16) for panels of at most 16 states, where the step is HBM-bound (arithmetic intensity b / 2 < 9.8 flop/B): twice the
-// workgroups, no MFMA spent on columns past the panel's width.  MFMA operand layout (as in engine_liouville.hip, verified there
-// against the library GEMM): lane l = (li = l & 15, lk = l >> 4) feeds A[i = li][k = lk] and B[k = lk][j = li] and receives
-// C[i = lk + 4 r][j = li] in accumulator register r.
+// One workgroup = one (16 TA) x (16 TB) tile of the panel (rows i0 .., states s0 ..) on the shared tile core: lane layout, k
+// quarters, pipelined k loop and wave-order sum are zgemm_mfma.h's.  TA = TB = 2 (32 x 32) for panels of more than 16 states:
+// 16 MFMAs per four 1-KiB loads, the MFMA rate decides (N = 4096, b = 64: 61 TFLOP/s); TA = TB = 1 (16 x 16) for panels of at
+// most 16 states, where the step is HBM-bound (arithmetic intensity b / 2 < 9.8 flop/B): twice the workgroups, no MFMA spent
+// on columns past the panel's width.  What is this kernel's own:
 //   A fragment: H[i0 + 16 a + li][k + lk]            (row-major H: 16 rows x 64 contiguous bytes per load)
 //   B fragment: X[(k + lk) b + s0 + 16 c + li]       (panel, state index contiguous: 4 rows x 256 contiguous bytes)
-// The four partial tiles are summed through LDS in wave order (deterministic), then the 4 TA TB (tile, register) pairs are dealt
-// to the four wavefronts, which apply the row epilogue of the fused term: element e = row * b + state, exactly as the sparse
-// panel kernels do.
+// and the epilogue: the wavefronts apply the row epilogue of the fused term to the (tile, register) pairs dealt to them:
+// element e = row * b + state, exactly as the sparse panel kernels do.
 template <class Op, class VT, int D, int TA, int TB>
 __global__ __launch_bounds__(256) void dense_zgemm_cheby_kernel(const VT* __restrict__ H, const double2* __restrict__ X, int n,
                                                                 int ncols, int b, Op op) {
@@ -166,9 +140,7 @@ __global__ __launch_bounds__(256) void dense_zgemm_cheby_kernel(const VT* __rest
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int row0 = blockIdx.x * (16 * TA), col0 = blockIdx.y * (16 * TB);
   const int ksteps = ncols >> 2;   // whole k-steps; the ncols & 3 inner indices left over: one masked step after the loop
-  const int per = (ksteps + 3) / 4;
-  const int sbeg = wave * per;
-  const int total = max(min(ksteps, sbeg + per) - sbeg, 0);
+  const KQuarter q = wave_quarter(ksteps, wave);
   const int li = lane & 15, lk = lane >> 4;
   constexpr unsigned ES = sizeof(VT);
   unsigned oa[TA], ob[TB];
@@ -183,16 +155,12 @@ __global__ __launch_bounds__(256) void dense_zgemm_cheby_kernel(const VT* __rest
     cb[c] = min(col0 + 16 * c + li, b - 1);
     ob[c] = ((unsigned)lk * (unsigned)b + (unsigned)cb[c]) * 16u;
   }
-  const VT* baseA = H + (size_t)row0 * (size_t)ncols + (size_t)sbeg * 4;
-  const double2* baseB = X + (size_t)sbeg * 4 * (size_t)b;
+  const VT* baseA = H + (size_t)row0 * (size_t)ncols + (size_t)q.sbeg * 4;
+  const double2* baseB = X + (size_t)q.sbeg * 4 * (size_t)b;
   const size_t strideB = (size_t)4 * (size_t)b;
 
-  v4d cr[TA][TB], ci[TA][TB];
-#pragma unroll
-  for (int a = 0; a < TA; ++a)
-#pragma unroll
-    for (int c = 0; c < TB; ++c) cr[a][c] = ci[a][c] = v4d{0.0, 0.0, 0.0, 0.0};
-
+  ZgemmTile<TA, TB> acc;
+  acc.zero();
   double2 fa[D][TA], fb[D][TB];
   auto load = [&](int slot) {
 #pragma unroll
@@ -202,76 +170,10 @@ __global__ __launch_bounds__(256) void dense_zgemm_cheby_kernel(const VT* __rest
     baseA += 4;
     baseB += strideB;
   };
-  auto mfma = [&](int slot) {   // 4 TA TB MFMAs (half for a real H); consecutive ones never share an accumulator where TA TB > 1
-#pragma unroll
-    for (int a = 0; a < TA; ++a)
-#pragma unroll
-      for (int c = 0; c < TB; ++c) {
-        cr[a][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[slot][a].x, fb[slot][c].x, cr[a][c], 0, 0, 0);
-        ci[a][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[slot][a].x, fb[slot][c].y, ci[a][c], 0, 0, 0);
-      }
-    if (CPLX) {
-      double nai[TA];
-#pragma unroll
-      for (int a = 0; a < TA; ++a) nai[a] = -fa[slot][a].y;
-#pragma unroll
-      for (int a = 0; a < TA; ++a)
-#pragma unroll
-        for (int c = 0; c < TB; ++c) {
-          cr[a][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(nai[a], fb[slot][c].y, cr[a][c], 0, 0, 0);
-          ci[a][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[slot][a].y, fb[slot][c].x, ci[a][c], 0, 0, 0);
-        }
-    }
-  };
+  auto step = [&](int slot) { acc.template step<CPLX>(fa[slot], fb[slot]); };
   constexpr int NM = (CPLX ? 4 : 2) * NT;          // MFMAs per k-step
   constexpr int NL = TA + TB;                      // refills per k-step
-  int s = 0;
-  if (total >= 2 * D - 1) {
-#pragma unroll
-    for (int d = 0; d < D - 1; ++d) {
-      load(d);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    for (; s + 2 * D - 1 <= total; s += D) {
-#pragma unroll
-      for (int j = 0; j < D; ++j) {
-        load((j + D - 1) % D);
-        mfma(j);
-#pragma unroll
-        for (int g = 0; g < NM; ++g) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                      // one MFMA
-          __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);                      // at most one vector-ALU instruction
-          __builtin_amdgcn_sched_group_barrier(0x004, 2, 0);                      // scalar work of the cursors
-          if (NM >= NL ? (g % (NM / NL) == (NM / NL) / 2) : true)
-            __builtin_amdgcn_sched_group_barrier(0x020, NM >= NL ? 1 : NL / NM, 0);   // the step's refills, spread over it
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    // here steps s .. s + D - 2 are loaded or in flight, in slots 0 .. D - 2
-    for (; s < total; s += D) {
-#pragma unroll
-      for (int j = 0; j < D; ++j) {
-        if (s + j < total) {
-          if (s + j + D - 1 < total) load((j + D - 1) % D);
-          mfma(j);
-        }
-      }
-    }
-  } else {
-#pragma unroll
-    for (int d = 0; d < D; ++d)
-      if (d < total) load(d);
-    for (; s < total; s += D) {
-#pragma unroll
-      for (int d = 0; d < D; ++d) {
-        if (s + d < total) {
-          mfma(d);
-          if (s + d + D < total) load(d);
-        }
-      }
-    }
-  }
+  pipelined_ksteps<D, NM, NL, (NM >= NL ? (NM / NL) / 2 : 0)>(q.nsteps, load, step);   // refills from the middle of their share of the MFMAs
   // ncols not a multiple of 4: one more k-step for the ncols & 3 inner indices left over (wavefront 0), the lanes past the
   // end masked out of the A fragment
   if ((ncols & 3) && wave == 0) {
@@ -286,44 +188,28 @@ __global__ __launch_bounds__(256) void dense_zgemm_cheby_kernel(const VT* __rest
     }
 #pragma unroll
     for (int c = 0; c < TB; ++c) fb[0][c] = X[(size_t)kc * b + cb[c]];
-    mfma(0);
+    step(0);
   }
-  // the 4 NT (tile, accumulator register) pairs of the workgroup's tile, NT per wavefront: pair p = wave NT + i is register
-  // r = p & 3 of MFMA tile p >> 2 (for the 32 x 32 tile: wavefront w finishes MFMA tile w).  Their row-local operands are
-  // requested before the partial tiles go through LDS.
+  // the row-local operands of this wavefront's NT (tile, register) pairs are requested before the partial tiles go through LDS
   typename Op::Pre pre[NT];
   int64_t el[NT];
   bool live[NT];
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
-    const int p = wave * NT + i, tile = p >> 2, r = p & 3;
-    const int row = row0 + (tile / TB) * 16 + lk + 4 * r, col = col0 + (tile % TB) * 16 + li;
+    const TilePair p = dealt_pair<NT>(wave, i);
+    const int row = row0 + (p.tile / TB) * 16 + lk + 4 * p.r, col = col0 + (p.tile % TB) * 16 + li;
     live[i] = row < n && col < b;
     el[i] = live[i] ? (int64_t)row * b + col : 0;
     if (live[i]) pre[i] = op.pre(el[i]);
   }
-#pragma unroll
-  for (int a = 0; a < TA; ++a)
-#pragma unroll
-    for (int c = 0; c < TB; ++c)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        red[wave][a * TB + c][0][r][lane] = cr[a][c][r];
-        red[wave][a * TB + c][1][r][lane] = ci[a][c][r];
-      }
+  acc.store(red, wave, lane);
   __syncthreads();
   double2 chk = make_double2(0.0, 0.0);
   double nrm = 0.0;
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
-    const int p = wave * NT + i, tile = p >> 2, r = p & 3;
-    double sr = red[0][tile][0][r][lane], si = red[0][tile][1][r][lane];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      sr += red[w][tile][0][r][lane];
-      si += red[w][tile][1][r][lane];
-    }
-    if (live[i]) op.row(el[i], make_double2(sr, si), pre[i], chk, nrm, el[i]);
+    const double2 v = wave_order_sum<NT>(red, dealt_pair<NT>(wave, i), lane);
+    if (live[i]) op.row(el[i], v, pre[i], chk, nrm, el[i]);
   }
 }
 
