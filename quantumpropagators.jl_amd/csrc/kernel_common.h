@@ -3,6 +3,8 @@
 // fused Chebyshev term and of the plain mat-vec, and the loaders of the row-block formats.  gfx950 only.
 #pragma once
 
+#include <type_traits>
+
 #include "device.h"
 
 namespace qp {
@@ -17,6 +19,17 @@ inline int ew_grid(int64_t n) {
   if (g < 1) g = 1;
   return (int)g;
 }
+
+// The values a launch streams: the real copy of an all-real operator (or of its value table) where there is one -- half the
+// bytes, the kernel's `double` instance --, else the complex values.  f: a generic lambda that launches with the typed pointer;
+// pointee_t<decltype(v)> is the kernel's value type.
+template <class F>
+inline void with_values(const double* real, const double2* cplx, F&& f) {
+  if (real) f(real);
+  else f(cplx);
+}
+template <class P>
+using pointee_t = std::remove_cv_t<std::remove_pointer_t<P>>;
 
 __device__ __forceinline__ void cfma(double2& s, const double2 a, const double2 b) {
   s.x = fma(a.x, b.x, s.x);
@@ -81,6 +94,14 @@ __device__ __forceinline__ double2 block_sum(double2 v, double2* lds4) {
   }
   __syncthreads();
   return r;
+}
+
+// One wavefront's LDS writes before the barrier are visible to its reads after it (a window or tile private to the wavefront:
+// no workgroup barrier, no waiting for other wavefronts)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // XCD-aware workgroup remap: hardware deals workgroups round-robin over the 8 XCDs

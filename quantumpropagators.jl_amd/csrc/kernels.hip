@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "kernel_common.h"
+#include "rowblock_sum.h"
 
 namespace qp {
 
@@ -58,22 +59,7 @@ __global__ __launch_bounds__(64 * WS) void rbcsr_spmv_kernel(const int64_t* __re
     row = b * kRB + lane;
     const int64_t rowc = row < nrows ? row : nrows - 1;
     if (PRE) pre = op.pre(rowc);
-#pragma unroll UNR
-    for (int q = 0; q < nq; ++q) {
-      const int4 c = ld_cols<NT>(colbytes, cm, q, lane, (int)rowc);
-      const double2 a0 = ld_val<NT>(v + (size_t)(4 * q + 0) * 64);
-      const double2 a1 = ld_val<NT>(v + (size_t)(4 * q + 1) * 64);
-      const double2 a2 = ld_val<NT>(v + (size_t)(4 * q + 2) * 64);
-      const double2 a3 = ld_val<NT>(v + (size_t)(4 * q + 3) * 64);
-      const double2 x0 = x[c.x];
-      const double2 x1 = x[c.y];
-      const double2 x2 = x[c.z];
-      const double2 x3 = x[c.w];
-      cfma(s0, a0, x0);
-      cfma(s1, a1, x1);
-      cfma(s0, a2, x2);
-      cfma(s1, a3, x3);
-    }
+    rowblock_quads<NT, NT, UNR>(s0, s1, colbytes, cm, v, nq, lane, (int)rowc, x);
     if (!PRE) pre = op.pre(rowc);
   }
   op.begin(lds);
@@ -169,24 +155,8 @@ __global__ __launch_bounds__(64 * WS) void hrb_spmv_kernel(const int64_t* __rest
         cfma_conj(s1, a3, x3);
       }
     };
-    auto upper = [&]() {
-#pragma unroll UNR
-      for (int q = 0; q < nuq; ++q) {
-        const int4 c = ld_cols<NT>(ucolbytes, ucm, q, lane, (int)rowc);
-        const double2 a0 = ld_val<false>(v + (size_t)(4 * q + 0) * 64);
-        const double2 a1 = ld_val<false>(v + (size_t)(4 * q + 1) * 64);
-        const double2 a2 = ld_val<false>(v + (size_t)(4 * q + 2) * 64);
-        const double2 a3 = ld_val<false>(v + (size_t)(4 * q + 3) * 64);
-        const double2 x0 = x[c.x];
-        const double2 x1 = x[c.y];
-        const double2 x2 = x[c.z];
-        const double2 x3 = x[c.w];
-        cfma(s0, a0, x0);
-        cfma(s1, a1, x1);
-        cfma(s0, a2, x2);
-        cfma(s1, a3, x3);
-      }
-    };
+    // (the values keep the default cache policy: the lower sections of the rows below re-read them through the L2)
+    auto upper = [&]() { rowblock_quads<NT, false, UNR>(s0, s1, ucolbytes, ucm, v, nuq, lane, (int)rowc, x); };
     // The common shape of a lattice / tensor-product H -- both sections stencil-encoded, two quads
     // each (z = 16) -- as straight-line code: all 16 value loads and 16 gathers of the row block are
     // issued before the first FMA (32 KiB in flight per wave instead of 4-8), which is what the
@@ -311,20 +281,25 @@ int spmv_grid_size(const DevMatrix& A) {
   return (int)((threads + kThreads - 1) / kThreads);
 }
 
+// one launch of a stored-operator mat-vec in the statistics; a launch over a row set counts as a mat-vec only where the set says so
+static void count_spmv_launch(Stats* st, const RowSet* rs) {
+  if (!st) return;
+  st->n_launch++;
+  if (!rs || rs->count) st->n_matvec++;
+}
+
+template <int I>
+using int_c = std::integral_constant<int, I>;
+
 template <class Op>
 static int launch_spmv(hipStream_t s, const DevMatrix& A, const double2* x, const Op& op, Stats* st,
                        const RowSet* rs = nullptr) {
   if (A.nrows == 0) return QP_OK;
-  int grid = spmv_grid_size(A);
   const int32_t* bmap = nullptr;
   int64_t nblk = A.nblocks;
   const SyncArgs sy = rs ? rs->sync : SyncArgs();
   static const Tuning kDefaults;
   const Tuning& tun = A.tun ? *A.tun : kDefaults;
-  // Eight instead of four row blocks per workgroup for the fused Chebyshev term wherever nothing counts
-  // workgroups of four: not with the per-workgroup check partials, and of the two launches of a split term only for the
-  // interior one (no completion signal, no mirror map; its wait threshold, given in workgroups of four, is halved and
-  // rounded down: the workgroup that straddles the threshold waits as well)
   // an operator with irregular columns: its column-blocked mirror (kernels_colblock.hip), whole-operator launches only
   if (!rs && A.cb && A.cb->valid && tun.colblock != 0) {
     bool launched = false;
@@ -333,13 +308,14 @@ static int launch_spmv(hipStream_t s, const DevMatrix& A, const double2* x, cons
     else rcb = launch_colblock_plain(s, A, x, op.e, tun, &launched);
     if (rcb != QP_OK) return rcb;
     if (launched) {
-      if (st) {
-        st->n_launch++;
-        st->n_matvec++;
-      }
+      count_spmv_launch(st, rs);
       return QP_OK;
     }
   }
+  // Eight instead of four row blocks per workgroup for the fused Chebyshev term wherever nothing counts
+  // workgroups of four: not with the per-workgroup check partials, and of the two launches of a split term only for the
+  // interior one (no completion signal, no mirror map; its wait threshold, given in workgroups of four, is halved and
+  // rounded down: the workgroup that straddles the threshold waits as well)
   bool wide_ok = false;
   SyncArgs sy8 = sy;
   if constexpr (std::is_same<Op, ChebyOp>::value) {
@@ -351,78 +327,66 @@ static int launch_spmv(hipStream_t s, const DevMatrix& A, const double2* x, cons
     bmap = rs->block_map;
     nblk = rs->nmap;
     if (nblk == 0) return QP_OK;
-    grid = (int)((nblk + kThreads / 64 - 1) / (kThreads / 64));
   }
+  constexpr int_c<kThreads / 64> ws4{};
+  constexpr int_c<8> ws8{};
+  // the variant switches of the two row-block formats: one case per kernel instance (tests/test_gpu_parity.py and tools/kbench.py run
+  // through them); `launch` is the format's lambda (variant, row blocks per workgroup, hand-off arguments)
+#define QP_CASE(VV)              \
+  case VV:                       \
+    launch(int_c<VV>(), ws4, sy); \
+    break;
   if (A.format == QP_FMT_RBCSR && A.cv && A.cv->valid && tun.value_dict != 0) {
     // few distinct values per block: one byte + a cached table line per entry instead of the value (kernels_coded.hip)
     int rcc;
     if constexpr (std::is_same<Op, ChebyOp>::value) rcc = launch_rbcsr_coded_cheby(s, A, x, op.e, nblk, bmap, sy, wide_ok);
     else rcc = launch_rbcsr_coded_plain(s, A, x, op.e, nblk, bmap, sy);
     if (rcc != QP_OK) return rcc;
-    if (st) {
-      st->n_launch++;
-      if (!rs || rs->count) st->n_matvec++;
-    }
+    count_spmv_launch(st, rs);
     return QP_OK;
   }
   if (A.format == QP_FMT_RBCSR) {
-#define QP_RB_CASE(VV)                                                                                   \
-  case VV:                                                                                               \
-    if (A.vals_r)                                                                                        \
-      hipLaunchKernelGGL((rbcsr_spmv_kernel<Op, VV, double>), dim3(grid), dim3(kThreads), 0, s, A.bptr, A.cmeta, \
-                         reinterpret_cast<const char*>(A.cols), A.vals_r, x, nblk, A.nrows, op, bmap, sy); \
-    else                                                                                                 \
-      hipLaunchKernelGGL((rbcsr_spmv_kernel<Op, VV, double2>), dim3(grid), dim3(kThreads), 0, s, A.bptr, A.cmeta, \
-                         reinterpret_cast<const char*>(A.cols), A.vals, x, nblk, A.nrows, op, bmap, sy);   \
-    break;
-    if constexpr (std::is_same<Op, ChebyOp>::value) {
-      // as for the Hermitian-packed kernel below: eight row blocks per workgroup for the plain fused term of a whole operator
-      if (wide_ok && (tun.rbcsr_variant & 7) == 7 && A.stored > A.nblocks * (int64_t)(kRB * 8)) {
-        const int g8 = (int)((nblk + 7) / 8);
-        if (A.vals_r)
-          hipLaunchKernelGGL((rbcsr_spmv_kernel<Op, 7, double, 8>), dim3(g8), dim3(512), 0, s, A.bptr, A.cmeta,
-                             reinterpret_cast<const char*>(A.cols), A.vals_r, x, nblk, A.nrows, op, bmap, sy8);
-        else
-          hipLaunchKernelGGL((rbcsr_spmv_kernel<Op, 7, double2, 8>), dim3(g8), dim3(512), 0, s, A.bptr, A.cmeta,
-                             reinterpret_cast<const char*>(A.cols), A.vals, x, nblk, A.nrows, op, bmap, sy8);
-        QP_HIP(hipGetLastError());
-        if (st) {
-          st->n_launch++;
-          if (!rs || rs->count) st->n_matvec++;
-        }
-        return QP_OK;
-      }
-    }
+    auto launch = [&](auto vv, auto ws, const SyncArgs& sya) {
+      constexpr int VV = decltype(vv)::value, WS = decltype(ws)::value;
+      with_values(A.vals_r, A.vals, [&](auto* v) {
+        hipLaunchKernelGGL((rbcsr_spmv_kernel<Op, VV, pointee_t<decltype(v)>, WS>), dim3((unsigned)((nblk + WS - 1) / WS)),
+                           dim3(64 * WS), 0, s, A.bptr, A.cmeta, reinterpret_cast<const char*>(A.cols), v, x, nblk, A.nrows, op,
+                           bmap, sya);
+      });
+    };
     // the deeper unroll (bit 2: 156-160 VGPRs, 3 wavefronts per SIMD) pays from three quads per row on; blocks of
     // at most two quads (8 entries per row: the Liouvillian of config C3) take the shallow one (88 VGPRs, 5 per
     // SIMD) -- at N = 2^18 that is one round of wavefronts instead of one and a third.  Same sums either way.
     int variant = tun.rbcsr_variant & 7;
-    if (A.stored <= A.nblocks * (int64_t)(kRB * 8)) variant &= ~4;
-    switch (variant) {
-      QP_RB_CASE(0)
-      QP_RB_CASE(1)
-      QP_RB_CASE(2)
-      QP_RB_CASE(3)
-      QP_RB_CASE(4)
-      QP_RB_CASE(5)
-      QP_RB_CASE(6)
-      QP_RB_CASE(7)
+    const bool deep = A.stored > A.nblocks * (int64_t)(kRB * 8);
+    if (!deep) variant &= ~4;
+    bool wide = false;
+    // as for the Hermitian-packed kernel below: eight row blocks per workgroup for the plain fused term of a whole operator
+    if constexpr (std::is_same<Op, ChebyOp>::value) {
+      wide = wide_ok && (tun.rbcsr_variant & 7) == 7 && deep;
+      if (wide) launch(int_c<7>(), ws8, sy8);
     }
-#undef QP_RB_CASE
+    if (!wide) switch (variant) {
+      QP_CASE(0)
+      QP_CASE(1)
+      QP_CASE(2)
+      QP_CASE(3)
+      QP_CASE(4)
+      QP_CASE(5)
+      QP_CASE(6)
+      QP_CASE(7)
+    }
   } else if (A.format == QP_FMT_HRB) {
-#define QP_HRB_CASE(VV)                                                                                  \
-  case VV:                                                                                               \
-    if (A.vals_r)                                                                                        \
-      hipLaunchKernelGGL((hrb_spmv_kernel<Op, VV, double>), dim3(grid), dim3(kThreads), 0, s, A.bptr, A.cmeta, \
-                         reinterpret_cast<const char*>(A.cols), A.vals_r, A.lptr, A.lcmeta,              \
-                         reinterpret_cast<const char*>(A.lcols), reinterpret_cast<const int4*>(A.lpos), x, \
-                         nblk, A.nrows, op, bmap, sy);                                 \
-    else                                                                                                 \
-      hipLaunchKernelGGL((hrb_spmv_kernel<Op, VV, double2>), dim3(grid), dim3(kThreads), 0, s, A.bptr, A.cmeta, \
-                         reinterpret_cast<const char*>(A.cols), A.vals, A.lptr, A.lcmeta,                \
-                         reinterpret_cast<const char*>(A.lcols), reinterpret_cast<const int4*>(A.lpos), x, \
-                         nblk, A.nrows, op, bmap, sy);                                 \
-    break;
+    auto launch = [&](auto vv, auto ws, const SyncArgs& sya) {
+      constexpr int VV = decltype(vv)::value, WS = decltype(ws)::value;
+      with_values(A.vals_r, A.vals, [&](auto* v) {
+        hipLaunchKernelGGL((hrb_spmv_kernel<Op, VV, pointee_t<decltype(v)>, WS>), dim3((unsigned)((nblk + WS - 1) / WS)),
+                           dim3(64 * WS), 0, s, A.bptr, A.cmeta, reinterpret_cast<const char*>(A.cols), v, A.lptr, A.lcmeta,
+                           reinterpret_cast<const char*>(A.lcols), reinterpret_cast<const int4*>(A.lpos), x, nblk, A.nrows, op,
+                           bmap, sya);
+      });
+    };
+    bool wide = false;
     if constexpr (std::is_same<Op, ChebyOp>::value) {
       // a lattice operator (one stencil repeated down the row blocks): the strip walk (kernels_walk.hip) -- whole operator,
       // no normalisation check, the gathered vector's own rows being the row-local operand; same sums as the kernels below
@@ -435,59 +399,39 @@ static int launch_spmv(hipStream_t s, const DevMatrix& A, const double2* x, cons
         const int rcw = launch_hrb_walk_cheby(s, A, x, op.e, tun, &launched, rs);
         if (rcw != QP_OK) return rcw;
         if (launched) {
-          if (st) {
-            st->n_launch++;
-            if (!rs || rs->count) st->n_matvec++;
-          }
+          count_spmv_launch(st, rs);
           return QP_OK;
         }
       }
       // eight row blocks per workgroup instead of four (see wide_ok above): half as many workgroups to dispatch, 36.3 ->
       // 35.2 us per term at N = 2^20 (profiles/r02/kbench_banded.txt); the same sums
-      if (wide_ok && (tun.rbcsr_variant & 31) == 15) {
-        const int g8 = (int)((nblk + 7) / 8);
-        if (A.vals_r)
-          hipLaunchKernelGGL((hrb_spmv_kernel<Op, 15, double, 8>), dim3(g8), dim3(512), 0, s, A.bptr, A.cmeta,
-                             reinterpret_cast<const char*>(A.cols), A.vals_r, A.lptr, A.lcmeta,
-                             reinterpret_cast<const char*>(A.lcols), reinterpret_cast<const int4*>(A.lpos), x, nblk, A.nrows, op,
-                             bmap, sy8);
-        else
-          hipLaunchKernelGGL((hrb_spmv_kernel<Op, 15, double2, 8>), dim3(g8), dim3(512), 0, s, A.bptr, A.cmeta,
-                             reinterpret_cast<const char*>(A.cols), A.vals, A.lptr, A.lcmeta,
-                             reinterpret_cast<const char*>(A.lcols), reinterpret_cast<const int4*>(A.lpos), x, nblk, A.nrows, op,
-                             bmap, sy8);
-        QP_HIP(hipGetLastError());
-        if (st) {
-          st->n_launch++;
-          if (!rs || rs->count) st->n_matvec++;
-        }
-        return QP_OK;
-      }
+      wide = wide_ok && (tun.rbcsr_variant & 31) == 15;
+      if (wide) launch(int_c<15>(), ws8, sy8);
     }
-    switch (tun.rbcsr_variant & 31) {
-      QP_HRB_CASE(0)
-      QP_HRB_CASE(1)
-      QP_HRB_CASE(2)
-      QP_HRB_CASE(3)
-      QP_HRB_CASE(4)
-      QP_HRB_CASE(5)
-      QP_HRB_CASE(6)
-      QP_HRB_CASE(7)
-      QP_HRB_CASE(8)
-      QP_HRB_CASE(15)
-      QP_HRB_CASE(31)
+    if (!wide) switch (tun.rbcsr_variant & 31) {
+      QP_CASE(0)
+      QP_CASE(1)
+      QP_CASE(2)
+      QP_CASE(3)
+      QP_CASE(4)
+      QP_CASE(5)
+      QP_CASE(6)
+      QP_CASE(7)
+      QP_CASE(8)
+      QP_CASE(15)
+      QP_CASE(31)
       default: return fail(QP_E_BAD_ARG, "rbcsr_variant %d has no Hermitian-packed kernel (0-8, 15, 31)", tun.rbcsr_variant);
     }
-#undef QP_HRB_CASE
   } else {
-#define QP_CSR_CASE(TT)                                                                                  \
-  case TT:                                                                                               \
-    if (A.vals_r)                                                                                        \
-      hipLaunchKernelGGL((csr_spmv_kernel<TT, Op, double>), dim3(grid), dim3(kThreads), 0, s, A.rowptr, A.cols, \
-                         A.vals_r, x, A.nrows, op);                                                      \
-    else                                                                                                 \
-      hipLaunchKernelGGL((csr_spmv_kernel<TT, Op, double2>), dim3(grid), dim3(kThreads), 0, s, A.rowptr, A.cols, \
-                         A.vals, x, A.nrows, op);                                                        \
+    auto launch_csr = [&](auto tt) {
+      with_values(A.vals_r, A.vals, [&](auto* v) {
+        hipLaunchKernelGGL((csr_spmv_kernel<decltype(tt)::value, Op, pointee_t<decltype(v)>>), dim3(spmv_grid_size(A)), dim3(kThreads), 0, s,
+                           A.rowptr, A.cols, v, x, A.nrows, op);
+      });
+    };
+#define QP_CSR_CASE(TT)         \
+  case TT:                      \
+    launch_csr(int_c<TT>());    \
     break;
     switch (A.lanes_per_row) {
       QP_CSR_CASE(2)
@@ -501,11 +445,9 @@ static int launch_spmv(hipStream_t s, const DevMatrix& A, const double2* x, cons
     }
 #undef QP_CSR_CASE
   }
+#undef QP_CASE
   QP_HIP(hipGetLastError());
-  if (st) {
-    st->n_launch++;
-    if (!rs || rs->count) st->n_matvec++;
-  }
+  count_spmv_launch(st, rs);
   return QP_OK;
 }
 

@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "kernel_common.h"
+#include "rowblock_sum.h"
 
 namespace qp {
 
@@ -71,54 +72,11 @@ __global__ __launch_bounds__(64 * kFusedWaves) void arnoldi_matvec_dots_kernel(
     if constexpr (CODED) {
       VT* __restrict__ tw = reinterpret_cast<VT*>(red_tile[wave]);
       const int64_t tp = tptr[bc];
-      const VT* __restrict__ tb = vals + (tp >> 9);
-      const int tlen = (int)(tp & 511);
-      if (t > 0) {      // the previous block's table reads are done before this block's table overwrites them
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i * 64 < tlen) tw[i * 64 + lane] = tb[min(i * 64 + lane, tlen - 1)];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const unsigned* __restrict__ cq = codes4 + (base >> 2) + lane;
-#pragma unroll 2
-      for (int q = 0; q < nq; ++q) {
-        const unsigned cw = __builtin_nontemporal_load(cq + (size_t)q * 64);
-        const int4 cc = ld_cols<true>(colbytes, cm, q, lane, (int)rowc);
-        const double2 x0 = x[cc.x];
-        const double2 x1 = x[cc.y];
-        const double2 x2 = x[cc.z];
-        const double2 x3 = x[cc.w];
-        const double2 a0 = ld_val<false>(tw + (cw & 255u));
-        const double2 a1 = ld_val<false>(tw + ((cw >> 8) & 255u));
-        const double2 a2 = ld_val<false>(tw + ((cw >> 16) & 255u));
-        const double2 a3 = ld_val<false>(tw + (cw >> 24));
-        cfma(s0, a0, x0);
-        cfma(s1, a1, x1);
-        cfma(s0, a2, x2);
-        cfma(s1, a3, x3);
-      }
+      if (t > 0) wave_lds_sync();   // the previous block's table reads are done before this block's table overwrites them
+      coded_stage_table(tw, vals, tp, lane);
+      rowblock_quads_coded<2>(s0, s1, colbytes, cm, codes4 + (base >> 2) + lane, tw, nq, lane, (int)rowc, x);
     } else {
-#pragma unroll 2
-    for (int q = 0; q < nq; ++q) {
-      const int4 cc = ld_cols<NT>(colbytes, cm, q, lane, (int)rowc);
-      const double2 a0 = ld_val<NT>(v + (size_t)(4 * q + 0) * 64);
-      const double2 a1 = ld_val<NT>(v + (size_t)(4 * q + 1) * 64);
-      const double2 a2 = ld_val<NT>(v + (size_t)(4 * q + 2) * 64);
-      const double2 a3 = ld_val<NT>(v + (size_t)(4 * q + 3) * 64);
-      const double2 x0 = x[cc.x];
-      const double2 x1 = x[cc.y];
-      const double2 x2 = x[cc.z];
-      const double2 x3 = x[cc.w];
-      cfma(s0, a0, x0);
-      cfma(s1, a1, x1);
-      cfma(s0, a2, x2);
-      cfma(s1, a3, x3);
-    }
+      rowblock_quads<NT, NT, 2>(s0, s1, colbytes, cm, v, nq, lane, (int)rowc, x);
     }
     if (t == 0 && e.norm_part) {
       np.x = wave_sum(np.x);
@@ -183,41 +141,16 @@ __global__ __launch_bounds__(64 * kFusedWaves) void arnoldi_matvec_dots_kernel(
       }
     }
   }
-  // 4 JT sums over the lanes of every wavefront, then over the wavefronts.  One cross-lane tree per value would be 80
-  // dependent chains at JT = 20; instead the lanes transpose eight values at a time through a wavefront-private LDS tile
-  // (row = lane, nine doubles wide: conflict-free both ways): lane l then owns value l % 8 and adds the entries of the
-  // eight lanes 8 (l / 8) .. 8 (l / 8) + 7 in order -- all 64 lanes busy, reads independent of one another --, one row
-  // shift folds the eight parts into four, and the workgroup's last stage adds 8 wavefronts x 4 parts per value in a
-  // fixed order.
+  // 4 JT sums over the lanes of every wavefront (rowblock_sum.h: four parts per wavefront and value), then the workgroup's last
+  // stage adds 8 wavefronts x 4 parts per value in a fixed order.
   {
     constexpr int NV = 4 * JT;
-    double* __restrict__ tile = red_tile[wave];
-    if constexpr (CODED) {      // the tile held the last block's table until here
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    const int tv = lane & 7, tp = lane >> 3;
-#pragma unroll
-    for (int ch = 0; ch < NV / 8; ++ch) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int id = 8 * ch + i;                       // value ids: c_k.re, c_k.im at 2 k, 2 k + 1; g_k at 2 JT + 2 k (+ 1)
-        const double2 a = id < 2 * JT ? c[id / 2] : g[(id - 2 * JT) / 2];
-        tile[lane * 9 + i] = (id & 1) ? a.y : a.x;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      double sum = tile[(tp * 8) * 9 + tv];
-#pragma unroll
-      for (int i = 1; i < 8; ++i) sum += tile[(tp * 8 + i) * 9 + tv];
-      sum += dpp_take<0x118, 0xf>(sum);                  // row_shr:8: part 2 r + 1 (lanes 8 .. 15 of a row) += part 2 r
-      if (tp & 1) red_parts[wave][tp >> 1][8 * ch + tv] = sum;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // this chunk's reads before the next chunk's writes
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
+    if constexpr (CODED) wave_lds_sync();   // the tile held the last block's table until here
+    // value ids: c_k.re, c_k.im at 2 k, 2 k + 1; g_k at 2 JT + 2 k (+ 1)
+    lane_transposed_sums(red_tile, red_parts, wave, lane, [&](int id) __attribute__((always_inline)) {
+      const double2 a = id < 2 * JT ? c[id / 2] : g[(id - 2 * JT) / 2];
+      return (id & 1) ? a.y : a.x;
+    });
     __syncthreads();
     if ((int)threadIdx.x < NV) {
       const int id = threadIdx.x;
@@ -236,35 +169,26 @@ __global__ __launch_bounds__(64 * kFusedWaves) void arnoldi_matvec_dots_kernel(
   }
 }
 
-template <int JT, bool NT>
-static void launch_instance_nt(hipStream_t s, const DevMatrix& A, const double2* x, const PlainEpi& e, const double2* Q,
-                               int64_t ldq, int j, double2* partials) {
-  if (A.vals_r)
-    hipLaunchKernelGGL((arnoldi_matvec_dots_kernel<JT, double, NT>), dim3(kRedBlocks), dim3(64 * kFusedWaves), 0, s, A.bptr,
-                       A.cmeta, reinterpret_cast<const char*>(A.cols), A.vals_r, x, A.nblocks, A.nrows, e, Q, ldq, j, partials, nullptr, nullptr);
-  else
-    hipLaunchKernelGGL((arnoldi_matvec_dots_kernel<JT, double2, NT>), dim3(kRedBlocks), dim3(64 * kFusedWaves), 0, s, A.bptr,
-                       A.cmeta, reinterpret_cast<const char*>(A.cols), A.vals, x, A.nblocks, A.nrows, e, Q, ldq, j, partials, nullptr, nullptr);
-}
 template <int JT>
 static void launch_instance(hipStream_t s, const DevMatrix& A, const double2* x, const PlainEpi& e, const double2* Q,
                             int64_t ldq, int j, double2* partials) {
+  auto launch = [&](auto nt, auto coded, const double* real, const double2* cplx, const unsigned* codes4, const int64_t* tptr) {
+    with_values(real, cplx, [&](auto* v) {
+      hipLaunchKernelGGL((arnoldi_matvec_dots_kernel<JT, pointee_t<decltype(v)>, decltype(nt)::value, decltype(coded)::value>),
+                         dim3(kRedBlocks), dim3(64 * kFusedWaves), 0, s, A.bptr, A.cmeta, reinterpret_cast<const char*>(A.cols), v, x,
+                         A.nblocks, A.nrows, e, Q, ldq, j, partials, codes4, tptr);
+    });
+  };
   // an operator with a value dictionary: codes + the block's table instead of the value plane
   if (A.cv && A.cv->valid && A.tun && A.tun->value_dict != 0) {
     const CodedVals& C = *A.cv;
-    const unsigned* codes4 = reinterpret_cast<const unsigned*>(C.codes);
-    if (C.use_real)
-      hipLaunchKernelGGL((arnoldi_matvec_dots_kernel<JT, double, true, true>), dim3(kRedBlocks), dim3(64 * kFusedWaves), 0, s, A.bptr,
-                         A.cmeta, reinterpret_cast<const char*>(A.cols), C.tab_r, x, A.nblocks, A.nrows, e, Q, ldq, j, partials, codes4, C.tptr);
-    else
-      hipLaunchKernelGGL((arnoldi_matvec_dots_kernel<JT, double2, true, true>), dim3(kRedBlocks), dim3(64 * kFusedWaves), 0, s, A.bptr,
-                         A.cmeta, reinterpret_cast<const char*>(A.cols), C.tab, x, A.nblocks, A.nrows, e, Q, ldq, j, partials, codes4, C.tptr);
+    launch(std::true_type(), std::true_type(), C.use_real ? C.tab_r : nullptr, C.tab, reinterpret_cast<const unsigned*>(C.codes), C.tptr);
     return;
   }
   // (only where the operator is large enough for the question to exist: a small one sits in the L2 with its basis)
   const bool nt = (double)A.stored * (A.vals_r ? 8.0 : 16.0) > 8.0 * 1024 * 1024;
-  if (nt) launch_instance_nt<JT, true>(s, A, x, e, Q, ldq, j, partials);
-  else launch_instance_nt<JT, false>(s, A, x, e, Q, ldq, j, partials);
+  if (nt) launch(std::true_type(), std::false_type(), A.vals_r, A.vals, nullptr, nullptr);
+  else launch(std::false_type(), std::false_type(), A.vals_r, A.vals, nullptr, nullptr);
 }
 
 // the largest j (basis vectors 0 .. j) with a kernel instance

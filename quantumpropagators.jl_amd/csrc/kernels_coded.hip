@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "kernel_common.h"
+#include "rowblock_sum.h"
 
 namespace qp {
 
@@ -48,38 +49,9 @@ __global__ __launch_bounds__(64 * WS) void rbcsr_coded_spmv_kernel(const int64_t
     row = b * kRB + lane;
     const int64_t rowc = row < nrows ? row : nrows - 1;
     pre = op.pre(rowc);
-    // the block's table into this wavefront's LDS window (at most 256 entries; a spin chain's block has a few dozen): the
-    // look-ups then go through the LDS crossbar, not through the vector L1 that the gathers of x keep busy
-    // (profiles/r05/value_dictionary.txt: 21 table reads per row through the L1 cost 8.5 of 45 us per term)
     TT* __restrict__ tw = tabs[wave];
-    {
-      const int64_t tp = tptr[b];
-      const TT* __restrict__ tb = tab + (tp >> 9);
-      const int tlen = (int)(tp & 511);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i * 64 < tlen) tw[i * 64 + lane] = tb[min(i * 64 + lane, tlen - 1)];   // (wave-uniform condition)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-#pragma unroll 4
-    for (int q = 0; q < nq; ++q) {
-      const unsigned cw = __builtin_nontemporal_load(cq + (size_t)q * 64);
-      const int4 c = ld_cols<true>(colbytes, cm, q, lane, (int)rowc);
-      const double2 x0 = x[c.x];
-      const double2 x1 = x[c.y];
-      const double2 x2 = x[c.z];
-      const double2 x3 = x[c.w];
-      const double2 a0 = ld_val<false>(tw + (cw & 255u));
-      const double2 a1 = ld_val<false>(tw + ((cw >> 8) & 255u));
-      const double2 a2 = ld_val<false>(tw + ((cw >> 16) & 255u));
-      const double2 a3 = ld_val<false>(tw + (cw >> 24));
-      cfma(s0, a0, x0);
-      cfma(s1, a1, x1);
-      cfma(s0, a2, x2);
-      cfma(s1, a3, x3);
-    }
+    coded_stage_table(tw, tab, tptr[b], lane);
+    rowblock_quads_coded<4>(s0, s1, colbytes, cm, cq, tw, nq, lane, (int)rowc, x);
   }
   op.begin(lds);
   if (row < nrows) op.row(row, make_double2(s0.x + s1.x, s0.y + s1.y), pre, chk, nrm, idx * kRB + lane);
@@ -93,12 +65,10 @@ static int launch_coded(hipStream_t s, const DevMatrix& A, const double2* x, con
   const CodedVals& C = *A.cv;
   const dim3 grid((unsigned)((nblk + WS - 1) / WS));
   const unsigned* codes4 = reinterpret_cast<const unsigned*>(C.codes);
-  if (C.use_real)
-    hipLaunchKernelGGL((rbcsr_coded_spmv_kernel<Op, double, WS>), grid, dim3(64 * WS), 0, s, A.bptr, A.cmeta,
-                       reinterpret_cast<const char*>(A.cols), codes4, C.tptr, C.tab_r, x, nblk, A.nrows, op, bmap, sy);
-  else
-    hipLaunchKernelGGL((rbcsr_coded_spmv_kernel<Op, double2, WS>), grid, dim3(64 * WS), 0, s, A.bptr, A.cmeta,
-                       reinterpret_cast<const char*>(A.cols), codes4, C.tptr, C.tab, x, nblk, A.nrows, op, bmap, sy);
+  with_values(C.use_real ? C.tab_r : nullptr, C.tab, [&](auto* tab) {
+    hipLaunchKernelGGL((rbcsr_coded_spmv_kernel<Op, pointee_t<decltype(tab)>, WS>), grid, dim3(64 * WS), 0, s, A.bptr, A.cmeta,
+                       reinterpret_cast<const char*>(A.cols), codes4, C.tptr, tab, x, nblk, A.nrows, op, bmap, sy);
+  });
   QP_HIP(hipGetLastError());
   return QP_OK;
 }

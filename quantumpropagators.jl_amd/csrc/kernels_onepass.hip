@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "kernel_common.h"
+#include "rowblock_sum.h"
 
 namespace qp {
 
@@ -118,11 +119,6 @@ __device__ __forceinline__ void onepass_solve(OpSolveLds& L, const OpSolveArgs& 
   }
   __syncthreads();
   if (wave != 0) return;
-  auto wsync = [] {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
   // Gram row / column t: g_k = <qh_k | qh_t>
   if (lane <= t) {
     const double2 gk = L.red[(t + 1) + lane];
@@ -134,7 +130,7 @@ __device__ __forceinline__ void onepass_solve(OpSolveLds& L, const OpSolveArgs& 
     }
   }
   if (lane < kOpLd) L.hs[lane] = L.gam[lane] = make_double2(0.0, 0.0);
-  wsync();
+  wave_lds_sync();
   const double gtt = L.Gs[t * kOpLd + t].x;
   const double nu_t = sqrt(gtt > 0.0 ? gtt : 0.0);
   if (lane == 0) L.nus[t] = nu_t;
@@ -142,7 +138,7 @@ __device__ __forceinline__ void onepass_solve(OpSolveLds& L, const OpSolveArgs& 
     // forward substitution, column by column: once h_k is final every later row subtracts G_ik h_k (row i accumulates in
     // ascending k: the order of the sequential projections, src/arnoldi.jl:84-87)
     if (lane <= t) L.rs[lane] = L.red[lane];
-    wsync();
+    wave_lds_sync();
     for (int k = 0; k <= t; ++k) {
       const double gkk = L.Gs[k * kOpLd + k].x;
       const double2 rk = L.rs[k];
@@ -157,7 +153,7 @@ __device__ __forceinline__ void onepass_solve(OpSolveLds& L, const OpSolveArgs& 
         r.y = fma(-gik.y, hk.x, r.y);
         L.rs[lane] = r;
       }
-      wsync();
+      wave_lds_sync();
     }
     // scale estimate: |a - sum h q|^2 ~ |a|^2 - sum |h_k|^2 G_kk
     double sub = 0.0;
@@ -182,7 +178,7 @@ __device__ __forceinline__ void onepass_solve(OpSolveLds& L, const OpSolveArgs& 
         A.svals[t + 1] = s_next;
       }
     }
-    wsync();
+    wave_lds_sync();
     // gamma_i = sum_{k >= i-1, k <= t} Hh[i][k] h_k, i <= t + 1 (lane i)
     if (lane <= t + 1) {
       double2 g = make_double2(0.0, 0.0);
@@ -315,6 +311,9 @@ __global__ __launch_bounds__(64 * WS) void arnoldi_onepass_kernel(
       (void)nqm;
       // (one block after the other: the gathers of a block are four to eight lines, and holding both blocks' values and operands at
       // once spilled 520 bytes per lane next to the 2 (JT + 1) accumulators; the sweeps over the basis rows below are interleaved)
+      // The quad loop of rowblock_sum.h (rowblock_quads<NT, NT, 2>), kept written out here: as a call it moved the AGPR count of five
+      // instances by two (JT = 8 / 12 with two blocks in flight, JT = 20 real) -- same VGPRs, scratch, LDS and occupancy, but these
+      // instances live on the allocator's edge (profiles/rowblock_sum_core.txt).  Same order: cols, values, gathers, s0 s1 s0 s1.
 #pragma unroll
       for (int j = 0; j < NBK; ++j) {
 #pragma unroll 2
@@ -456,34 +455,16 @@ __global__ __launch_bounds__(64 * WS) void arnoldi_onepass_kernel(
       g[JT].x += qn[j].x * qn[j].x + qn[j].y * qn[j].y;
     }
   }
-  // NV sums over the lanes of every wavefront, then over the wavefronts (the transpose of kernels_arnoldi.hip: eight values
-  // at a time through a wavefront-private LDS tile, row = lane, nine doubles wide; fixed order, no atomics)
+  // NV sums over the lanes of every wavefront (rowblock_sum.h), then over the wavefronts; fixed order, no atomics
   {
-    double* __restrict__ tile = red_tile[wave];
-    const int tv = lane & 7, tp = lane >> 3;
-#pragma unroll
-    for (int ch = 0; ch < NV / 8; ++ch) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int id = 8 * ch + i;   // d_k.re, d_k.im at 2 k, 2 k + 1 (k <= JT); g_k at 2 (JT + 1) + 2 k (+ 1); |a|^2 at 4 (JT + 1)
-        double val = 0.0;
-        if (id < 2 * (JT + 1)) val = (id & 1) ? d[id / 2].y : d[id / 2].x;
-        else if (id < 4 * (JT + 1)) val = (id & 1) ? g[(id - 2 * (JT + 1)) / 2].y : g[(id - 2 * (JT + 1)) / 2].x;
-        else if (id == 4 * (JT + 1)) val = aa;
-        tile[lane * 9 + i] = val;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      double sum = tile[(tp * 8) * 9 + tv];
-#pragma unroll
-      for (int i = 1; i < 8; ++i) sum += tile[(tp * 8 + i) * 9 + tv];
-      sum += dpp_take<0x118, 0xf>(sum);   // row_shr:8: part 2 r + 1 += part 2 r
-      if (tp & 1) red_parts[wave][tp >> 1][8 * ch + tv] = sum;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
+    // d_k.re, d_k.im at 2 k, 2 k + 1 (k <= JT); g_k at 2 (JT + 1) + 2 k (+ 1); |a|^2 at 4 (JT + 1)
+    lane_transposed_sums(red_tile, red_parts, wave, lane, [&](int id) __attribute__((always_inline)) {
+      double val = 0.0;
+      if (id < 2 * (JT + 1)) val = (id & 1) ? d[id / 2].y : d[id / 2].x;
+      else if (id < 4 * (JT + 1)) val = (id & 1) ? g[(id - 2 * (JT + 1)) / 2].y : g[(id - 2 * (JT + 1)) / 2].x;
+      else if (id == 4 * (JT + 1)) val = aa;
+      return val;
+    });
     __syncthreads();
     if ((int)threadIdx.x < NV) {
       const int id = threadIdx.x;
@@ -515,14 +496,11 @@ template <int JT, bool NT, bool MV>
 static void launch_op_instance(hipStream_t s, const DevMatrix& A, const double2* a_in, const double2* Q, int64_t ldq, int nb,
                                const OpSolveArgs& S, double s0, double2* q_out, double2* a_out, double2* partials) {
   constexpr int WS = JT <= 4 ? 8 : 4;
-  if (A.vals_r)
-    hipLaunchKernelGGL((arnoldi_onepass_kernel<JT, double, NT, MV, WS>), dim3(kRedBlocks), dim3(64 * WS), 0, s, A.bptr, A.cmeta,
-                       reinterpret_cast<const char*>(A.cols), A.vals_r, a_in, A.nblocks, A.nrows, Q, ldq, nb, S, s0, q_out, a_out,
+  with_values(A.vals_r, A.vals, [&](auto* v) {
+    hipLaunchKernelGGL((arnoldi_onepass_kernel<JT, pointee_t<decltype(v)>, NT, MV, WS>), dim3(kRedBlocks), dim3(64 * WS), 0, s, A.bptr,
+                       A.cmeta, reinterpret_cast<const char*>(A.cols), v, a_in, A.nblocks, A.nrows, Q, ldq, nb, S, s0, q_out, a_out,
                        partials);
-  else
-    hipLaunchKernelGGL((arnoldi_onepass_kernel<JT, double2, NT, MV, WS>), dim3(kRedBlocks), dim3(64 * WS), 0, s, A.bptr, A.cmeta,
-                       reinterpret_cast<const char*>(A.cols), A.vals, a_in, A.nblocks, A.nrows, Q, ldq, nb, S, s0, q_out, a_out,
-                       partials);
+  });
 }
 
 bool arnoldi_onepass_fits(const DevMatrix& A, int m, int nvec) {

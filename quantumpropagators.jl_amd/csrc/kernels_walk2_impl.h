@@ -172,9 +172,7 @@ __global__ __launch_bounds__(64 * kWalk2Waves) void hrb_walk2_kernel(const VT* _
       for (int i = 1; i < NN; ++i) own = sel2(hq == i, cu.ua[Z0 + i], own);
       xwin[ha_pos] = sel2(ha_on, cu.ha, own);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     double2 fy[K], fzl[K], fzu[K], na[NN], nxl[NN], nxu[NN];
 #pragma unroll
     for (int m = 1; m <= K; ++m) {
@@ -227,9 +225,7 @@ __global__ __launch_bounds__(64 * kWalk2Waves) void hrb_walk2_kernel(const VT* _
     yr[2 * K] = yv;
     // ---- this step's far values into the FIFOs, the windows of phase Z (block t - K: its y and its near values; no halos -- the
     //      lanes that form z have their near neighbours inside the chunk)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // phase Y's window / FIFO reads before the writes below
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();   // phase Y's window / FIFO reads before the writes below
 #pragma unroll
     for (int m = 1; m <= K; ++m) {
       fifo[(foff(m) + hp[m - 1]) * kRB + lane] = cu.ua[Z0 + NN + (m - 1)];
@@ -238,9 +234,7 @@ __global__ __launch_bounds__(64 * kWalk2Waves) void hrb_walk2_kernel(const VT* _
     xwin[kWalkHalo + lane] = yr[K];
 #pragma unroll
     for (int i = 0; i < NN; ++i) xwin[XW + i * AW + kWalkHalo + lane] = nh[0][Z0 + i];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     {
       double2 za[NN], zyl[NN], zyu[NN];
 #pragma unroll
@@ -293,9 +287,7 @@ __global__ __launch_bounds__(64 * kWalk2Waves) void hrb_walk2_kernel(const VT* _
       if (owner && c >= j0 && c < j1 && row < ze) opl2.finish(row, zv, pre);
     }
     // ---- one step down the strip column
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // phase Z's window reads before the next step's window writes
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();   // phase Z's window reads before the next step's window writes
 #pragma unroll
     for (int i = 0; i < 2 * K; ++i) {
       xr[i] = xr[i + 1];

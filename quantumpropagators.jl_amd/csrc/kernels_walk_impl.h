@@ -421,9 +421,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void hrb_walk_kernel(const VT* __r
       xwin[ha_pos] = sel2(ha_on, cu.ha, own);
     }
     // the lanes of this wavefront exchange data through its own window: order the writes before the reads
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     // every operand that comes out of LDS first (independent reads, one wait), then the arithmetic
     double2 fa[KF], na[NN], nxl[NN], nxu[NN];
 #pragma unroll
@@ -511,9 +509,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void hrb_walk_kernel(const VT* __r
     const int64_t row = row0 + lane;
     if (in_strip && row < rend) opl.row(row, make_double2(s0.x + s1.x, s0.y + s1.y), pre, chk, nrm, 0);
     // ---- one step down the strip column
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // this step's window / FIFO reads before the writes below
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();   // this step's window / FIFO reads before the writes below
 #pragma unroll
     for (int m = 1; m <= K; ++m) {
 #pragma unroll

@@ -3,8 +3,8 @@ csrc/engine_liouville.hip, the dense panel Chebyshev term of csrc/kernels_dense.
 shared tile core existed: SHA-256 digests of their outputs, recorded from the build of the commit before it, in
 tests/golden/zgemm_bits_parent.json.
 
-The inputs are exact: 31-bit integers of a quadratic integer recurrence modulo a prime, scaled by a power of two (no
-random-number library), so the digests depend on the kernels alone.  The products of two such values do not fit a double:
+The inputs are exact (tests/exact_inputs.py): 31-bit integers of a quadratic integer recurrence modulo a prime, scaled by a power
+of two (no random-number library), so the digests depend on the kernels alone.  The products of two such values do not fit a double:
 every accumulate rounds, and a wrong operand, pipeline slot, tail or summation order changes the digest, while the order in
 which independent accumulators are issued cannot.  The Lindblad operators are few-bit integers, so that the one library GEMM
 on the way (G = sum_k A_k^+ A_k at creation) is exact in any order.
@@ -18,7 +18,6 @@ branch from 2 D - 1 = 11 k-steps):
   dense panel           (33, 8) 16 x 16 tile, short branch, ncols & 3 = 1; (179, 5) 16 x 16, steady branch, ncols & 3 = 3;
                         (1540, 33) 16 x 32 tile; (3076, 33) 32 x 32 tile with edge rows and edge columns
 """
-import hashlib
 import json
 import os
 import sys
@@ -28,26 +27,12 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import qprop_amd.lib as L  # noqa: E402
+from exact_inputs import cmat as _cmat, digest as _digest, seq as _seq  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 FIXTURE = os.path.join(ROOT, "tests", "golden", "zgemm_bits_parent.json")
-P = 2147483647      # 2^31 - 1
-
-
-def _seq(count, seed):
-    """x_i = (1103515245 i^2 + 1664525 i + seed) mod P, centred: the integer recurrence x_{i+1} = x_i + d_i,
-    d_{i+1} = d_i + 2 * 1103515245 (mod P) in closed form, vectorised.  Integers in (-2^30, 2^30) as float64."""
-    i = np.arange(count, dtype=np.int64) % P
-    x = ((i * i) % P * 1103515245 + i * 1664525 + seed) % P
-    return (x - P // 2).astype(np.float64)
-
-
-def _cmat(rows, cols, seed, shift, real=False):
-    """rows x cols, entries (integer) 2^-shift, |entry| < 2^(30 - shift)"""
-    re = _seq(rows * cols, seed).reshape(rows, cols)
-    im = np.zeros_like(re) if real else _seq(rows * cols, seed + 7919).reshape(rows, cols)
-    return np.ldexp(re, -shift) + 1j * np.ldexp(im, -shift)
 
 
 def _small_int_mat(n, seed):
@@ -55,10 +40,6 @@ def _small_int_mat(n, seed):
     re = np.round(_seq(n * n, seed) * 2.0 ** -27).reshape(n, n)
     im = np.round(_seq(n * n, seed + 104729) * 2.0 ** -27).reshape(n, n)
     return (re + 1j * im) / 16.0
-
-
-def _digest(a):
-    return hashlib.sha256(np.ascontiguousarray(a, dtype=np.complex128).tobytes()).hexdigest()
 
 
 @pytest.fixture(scope="module")
