@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "kernel_common.h"
+#include "panel_rowsum.h"
 
 namespace qp {
 
@@ -63,21 +64,11 @@ __global__ __launch_bounds__(kThreads) void csr_spmm_kernel(const int64_t* __res
       s_col[rl][sl] = Op::kStream ? __builtin_nontemporal_load(cols + p0 + k0 + sl) : cols[p0 + k0 + sl];
     }
     __syncthreads();
-    const int cnt = min(CH, len - k0);
-    if (active) {
-      int k = 0;
-      for (; k + 3 < cnt; k += 4) {
-        const double2 x0 = X[(int64_t)s_col[rl][k] * b + st];
-        const double2 x1 = X[(int64_t)s_col[rl][k + 1] * b + st];
-        const double2 x2 = X[(int64_t)s_col[rl][k + 2] * b + st];
-        const double2 x3 = X[(int64_t)s_col[rl][k + 3] * b + st];
-        cfma(acc0, s_val[rl][k], x0);
-        cfma(acc1, s_val[rl][k + 1], x1);
-        cfma(acc0, s_val[rl][k + 2], x2);
-        cfma(acc1, s_val[rl][k + 3], x3);
-      }
-      for (; k < cnt; ++k) cfma(acc0, s_val[rl][k], X[(int64_t)s_col[rl][k] * b + st]);
-    }
+    // the row sum of panel_rowsum.h, chunk by chunk (CH is a multiple of four: every chunk but the row's last is whole groups, so the
+    // rule holds for the row); groups of four: eight gathers in flight take 92 - 102 VGPRs instead of 70 and two or three of the seven waves per SIMD
+    if (active)
+      panel_row_sum<4>(acc0, acc1, min(CH, len - k0), [&](int k) { return s_val[rl][k]; },
+                    [&](int k) { return X[(int64_t)s_col[rl][k] * b + st]; });
   }
   if (active) op.row(e, make_double2(acc0.x + acc1.x, acc0.y + acc1.y), pre, chk, nrm, e);
 }
@@ -98,12 +89,6 @@ __global__ __launch_bounds__(kThreads) void csr_spmm_kernel(const int64_t* __res
 // just after, and the window a wave can hit in L2 shrinks to (2 a_max + 1) sw rows.  Any
 // permutation gives the same values bit for bit (rows are independent); it only moves traffic.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double readlane_f64(double v, int l) {   // l wave-uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-
 // Scalar-memory variant (knob spmm_rw = 0): the row's entries are wave-uniform, so they can be fetched by the
 // scalar unit (s_load: value and column straight into SGPRs, which the FMAs and the gather addresses take as
 // operands) instead of one entry per lane + v_readlane broadcasts -- five VALU instructions per entry less.
@@ -128,35 +113,8 @@ __device__ __forceinline__ void spmm_row_scalar_entries(const int64_t* __restric
   double2 acc0 = make_double2(0.0, 0.0), acc1 = make_double2(0.0, 0.0);
   double2 chk = make_double2(0.0, 0.0);
   double nrm = 0.0;
-  int k = 0;
-  // sums in the order of csr_spmm_kernel (groups of four alternating between two partial sums, remainder into the first)
-  for (; k + 7 < len; k += 8) {
-    double2 x[8], a[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      x[u] = Xs[(int64_t)rc[k + u] * b];
-      a[u] = rv[k + u];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; u += 2) {
-      cfma(acc0, a[u], x[u]);
-      cfma(acc1, a[u + 1], x[u + 1]);
-    }
-  }
-  if (k + 3 < len) {
-    double2 x[4], a[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      x[u] = Xs[(int64_t)rc[k + u] * b];
-      a[u] = rv[k + u];
-    }
-    cfma(acc0, a[0], x[0]);
-    cfma(acc1, a[1], x[1]);
-    cfma(acc0, a[2], x[2]);
-    cfma(acc1, a[3], x[3]);
-    k += 4;
-  }
-  for (; k < len; ++k) cfma(acc0, rv[k], Xs[(int64_t)rc[k] * b]);
+  // the row sum of panel_rowsum.h: values and columns through scalar loads, up to eight gathers in flight
+  panel_row_sum(acc0, acc1, len, [&](int k) { return rv[k]; }, [&](int k) { return Xs[(int64_t)rc[k] * b]; });
   if (active) op.row(e, make_double2(acc0.x + acc1.x, acc0.y + acc1.y), pre, chk, nrm, e);
 }
 
@@ -180,8 +138,8 @@ __global__ __launch_bounds__(64 * WS) void spmm_rows_smem_kernel(const int64_t* 
 // Sixteen wavefronts = the sixteen rows r0 + i g + j of the tile, lane = state.  The workgroup first loads the 16 + 8 K + 8 NN
 // distinct panel rows its rows read -- slots [(4 + 2 K) strip steps][4 columns], then [4 strip steps][2 NN near-halo columns] --
 // five per wavefront, issued before the row-local streams so that the barrier waits on them as little as possible; after the
-// barrier every wavefront sums its row exactly as spmm_rows_smem_kernel does (same entries, same order, same two partial sums:
-// the same bits), with ds_read_b128 in place of the gathers.  Measured on the bare loop (profiles/r06/panel_tile_probe.txt):
+// barrier every wavefront sums its row by the rule of panel_rowsum.h (same entries, same order, same two partial sums as
+// spmm_rows_smem_kernel: the same bits), with ds_read_b128 in place of the gathers.  Measured on the bare loop (profiles/r06/panel_tile_probe.txt):
 // larger tiles or tiles held in registers lose to the occupancy they cost; two workgroups of 80 KiB per compute unit do not.
 // ---------------------------------------------------------------------------
 template <class Op>
@@ -246,30 +204,16 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
   double2 acc0 = make_double2(0.0, 0.0), acc1 = make_double2(0.0, 0.0);
   double2 chk = make_double2(0.0, 0.0);
   double nrm = 0.0;
-  // sums in the order of spmm_rows_smem_kernel / csr_spmm_kernel: groups of eight alternating between the two partial sums while
-  // eight entries are left, then one group of four, then the last one to three entries into the first sum
+  // panel_row_sum (panel_rowsum.h) as a skeleton over compile-time entry numbers -- v_readlane takes its lane as an immediate, and the
+  // kernel keeps the registers that its eight wavefronts per SIMD beside 80 KiB of LDS allow --: the same rule through the same
+  // group primitive, operands four at a time
 #pragma unroll
   for (int kk = 0; kk < kSpmmTileMaxEntries; kk += 8) {
-    if (kk + 7 < len) {      // (operands four at a time: the order of the sums is that of a group of eight, the registers are half)
-#pragma unroll
-      for (int h = 0; h < 8; h += 4) {
-        double2 x[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) x[u] = xk(kk + h + u);
-        cfma(acc0, ak(kk + h), x[0]);
-        cfma(acc1, ak(kk + h + 1), x[1]);
-        cfma(acc0, ak(kk + h + 2), x[2]);
-        cfma(acc1, ak(kk + h + 3), x[3]);
-      }
+    if (kk + 7 < len) {
+      panel_group<8, 4, false>(acc0, acc1, kk, ak, xk);
     } else if (kk < len) {
       if (kk + 3 < len) {
-        double2 x[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) x[u] = xk(kk + u);
-        cfma(acc0, ak(kk), x[0]);
-        cfma(acc1, ak(kk + 1), x[1]);
-        cfma(acc0, ak(kk + 2), x[2]);
-        cfma(acc1, ak(kk + 3), x[3]);
+        panel_group<4, 4, false>(acc0, acc1, kk, ak, xk);
 #pragma unroll
         for (int u = 4; u < 7; ++u)
           if (kk + u < len) cfma(acc0, ak(kk + u), xk(kk + u));
@@ -286,7 +230,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 // One wavefront walks RW consecutive positions of the row walk.  The dependent loads in front of a
 // row's gathers (walk position -> row, row pointers, the row's entries) are issued for all RW rows
 // together, so a row costs one round of up to 16 gathers instead of a chain of four memory latencies.
-template <class Op, int RW, int G>
+template <class Op, int RW>
 __global__ __launch_bounds__(kThreads) void spmm_rows_kernel(const int64_t* __restrict__ rowptr,
                                                              const int32_t* __restrict__ cols,
                                                              const double2* __restrict__ vals,
@@ -355,26 +299,10 @@ __global__ __launch_bounds__(kThreads) void spmm_rows_kernel(const int64_t* __re
           cc = Op::kStream ? __builtin_nontemporal_load(cols + p0[l] + k0 + lane) : cols[p0[l] + k0 + lane];
         }
       }
-      // the sums run in the order of csr_spmm_kernel: within groups of four, entries alternate between
-      // two partial sums; the remainder goes to the first.  Up to G gathers in flight.
-      int k = 0;
-#define QP_SPMM_GROUP(GG)                                                                              \
-  {                                                                                                    \
-    double2 x[GG];                                                                                     \
-    _Pragma("unroll") for (int u = 0; u < GG; ++u) x[u] = Xs[(int64_t)__builtin_amdgcn_readlane(cc, k + u) * b]; \
-    _Pragma("unroll") for (int u = 0; u < GG; u += 2) {                                                \
-      cfma(acc0, make_double2(readlane_f64(cv.x, k + u), readlane_f64(cv.y, k + u)), x[u]);            \
-      cfma(acc1, make_double2(readlane_f64(cv.x, k + u + 1), readlane_f64(cv.y, k + u + 1)), x[u + 1]); \
-    }                                                                                                  \
-    k += GG;                                                                                           \
-  }
-      if (G >= 16)
-        while (k + 15 < cnt) QP_SPMM_GROUP(16)
-      while (k + 7 < cnt) QP_SPMM_GROUP(8)
-      if (k + 3 < cnt) QP_SPMM_GROUP(4)
-#undef QP_SPMM_GROUP
-      for (; k < cnt; ++k)
-        cfma(acc0, make_double2(readlane_f64(cv.x, k), readlane_f64(cv.y, k)), Xs[(int64_t)__builtin_amdgcn_readlane(cc, k) * b]);
+      // the row sum of panel_rowsum.h, chunk by chunk (every chunk but the row's last holds 64 entries: whole groups); up to eight
+      // gathers in flight
+      panel_row_sum(acc0, acc1, cnt, [&](int k) { return make_double2(readlane_f64(cv.x, k), readlane_f64(cv.y, k)); },
+                    [&](int k) { return Xs[(int64_t)__builtin_amdgcn_readlane(cc, k) * b]; });
     }
     res[l] = make_double2(acc0.x + acc1.x, acc0.y + acc1.y);
   }
@@ -386,70 +314,50 @@ __global__ __launch_bounds__(kThreads) void spmm_rows_kernel(const int64_t* __re
     }
 }
 
-// knob spmm_nt -- nontemporal matrix and row-local streams in the batched kernel: 0 never, 2 always,
+// knob spmm_nt -- nontemporal matrix and row-local streams in the batched kernels: 0 never, 2 always,
 // 1 when one panel vector is larger than what the caches could keep until the next launch anyway
-template <int TS>
-static void launch_spmm_cheby_t(hipStream_t s, const int64_t* rowptr, const int32_t* cols, const double2* vals,
-                                const double2* X, int64_t nrows, int b, const ChebyEpi& e, int spmm_nt) {
-  const int rpw = kThreads / TS;
-  dim3 grid((unsigned)((nrows + rpw - 1) / rpw), (unsigned)((b + TS - 1) / TS));
-  const bool nt = spmm_nt == 2 || (spmm_nt == 1 && (double)nrows * b * sizeof(double2) >= 128.0 * 1024 * 1024);
-  if (nt) {
-    ChebyOpT<true> op{e};
-    hipLaunchKernelGGL((csr_spmm_kernel<ChebyOpT<true>, TS>), grid, dim3(kThreads), 0, s, rowptr, cols, vals, X, nrows, b, op);
-  } else {
-    ChebyOp op{e};
-    hipLaunchKernelGGL((csr_spmm_kernel<ChebyOp, TS>), grid, dim3(kThreads), 0, s, rowptr, cols, vals, X, nrows, b, op);
-  }
-}
-
 static bool spmm_streams_nt(const Tuning& tun, int64_t nrows, int b) {
   return tun.spmm_nt == 2 || (tun.spmm_nt == 1 && (double)nrows * b * sizeof(double2) >= 128.0 * 1024 * 1024);
 }
 
-template <class Op>
-static void launch_rows_smem(hipStream_t s, const int64_t* rowptr, const int32_t* cols, const double2* vals, const double2* X,
-                             int64_t nrows, int b, const Op& op, const int32_t* order) {
-  constexpr int WS = 8;
-  dim3 grid((unsigned)((nrows + WS - 1) / WS), (unsigned)((b + 63) / 64));
-  hipLaunchKernelGGL((spmm_rows_smem_kernel<Op, WS>), grid, dim3(64 * WS), 0, s, rowptr, cols, vals, X, nrows, b, op, order);
+// f(op) with the Chebyshev epilogue of the panel kernels, with or without nontemporal streams: the one place a launch chooses
+// between the two instances (as with_values(), kernel_common.h, does for the two copies of the values)
+template <class F>
+static int with_cheby_op(const ChebyEpi& e, bool nt, F&& f) {
+  if (nt) return f(ChebyOpT<true>{e});
+  return f(ChebyOp{e});
 }
 
-template <class Op>
-static int launch_tiles_t(hipStream_t s, const int64_t* rowptr, const int32_t* cols, const double2* vals, const double2* X,
-                          int64_t nrows, int b, const Op& op, const SpmmTiles& P) {
-  const size_t lds = (size_t)P.T * 64 * sizeof(double2);
-  // more than the 64 KiB a launch may ask for by default: a property of the function on a device, set once per device (the call
-  // is a slow one: hundreds of microseconds on the host)
-  static std::atomic<uint64_t> done{0};
-  int dev = 0;
-  QP_HIP(hipGetDevice(&dev));
-  if (dev >= 64 || !(done.load(std::memory_order_acquire) >> dev & 1)) {
-    QP_HIP(hipFuncSetAttribute((const void*)spmm_tile_kernel<Op>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-    if (dev < 64) done.fetch_or((uint64_t)1 << dev, std::memory_order_release);
-  }
-  dim3 grid((unsigned)(P.ntiles + (P.nrest + 15) / 16), (unsigned)((b + 63) / 64));
-  hipLaunchKernelGGL((spmm_tile_kernel<Op>), grid, dim3(1024), lds, s, rowptr, cols, vals, X, nrows, b, op, P.tiles, P.tab, P.shape.nd,
-                     P.T, (int)P.ntiles, P.rest, (int)P.nrest);
-  return QP_OK;
+// one fused panel term in the statistics: the matrix once (20 bytes per entry, the row pointers), 80 bytes per element of the panel
+static void count_panel_term(Stats* st, int64_t nrows, int64_t nnz, int b) {
+  if (!st) return;
+  st->n_launch++;
+  st->n_matvec++;
+  st->spmv_bytes += 20.0 * (double)nnz + 4.0 * (double)(nrows + 1) + 80.0 * (double)nrows * b;
 }
 
 int launch_spmm_tile_cheby(hipStream_t s, const int64_t* rowptr, const int32_t* cols, const double2* vals, const double2* X,
                            int64_t nrows, int64_t nnz, int b, const ChebyEpi& e, const Tuning& tun, const SpmmTiles& P, Stats* st) {
   if (nrows == 0) return QP_OK;
-  if (spmm_streams_nt(tun, nrows, b)) {
-    ChebyOpT<true> op{e};
-    if (const int rc = launch_tiles_t(s, rowptr, cols, vals, X, nrows, b, op, P)) return rc;
-  } else {
-    ChebyOp op{e};
-    if (const int rc = launch_tiles_t(s, rowptr, cols, vals, X, nrows, b, op, P)) return rc;
-  }
+  const int rc = with_cheby_op(e, spmm_streams_nt(tun, nrows, b), [&](auto op) -> int {
+    using Op = decltype(op);
+    // more than the 64 KiB a launch may ask for by default: a property of the function on a device, set once per device (the call
+    // is a slow one: hundreds of microseconds on the host)
+    static std::atomic<uint64_t> done{0};
+    int dev = 0;
+    QP_HIP(hipGetDevice(&dev));
+    if (dev >= 64 || !(done.load(std::memory_order_acquire) >> dev & 1)) {
+      QP_HIP(hipFuncSetAttribute((const void*)spmm_tile_kernel<Op>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+      if (dev < 64) done.fetch_or((uint64_t)1 << dev, std::memory_order_release);
+    }
+    dim3 grid((unsigned)(P.ntiles + (P.nrest + 15) / 16), (unsigned)((b + 63) / 64));
+    hipLaunchKernelGGL((spmm_tile_kernel<Op>), grid, dim3(1024), (size_t)P.T * 64 * sizeof(double2), s, rowptr, cols, vals, X, nrows, b,
+                       op, P.tiles, P.tab, P.shape.nd, P.T, (int)P.ntiles, P.rest, (int)P.nrest);
+    return QP_OK;
+  });
+  if (rc) return rc;
   QP_HIP(hipGetLastError());
-  if (st) {
-    st->n_launch++;
-    st->n_matvec++;
-    st->spmv_bytes += 20.0 * (double)nnz + 4.0 * (double)(nrows + 1) + 80.0 * (double)nrows * b;
-  }
+  count_panel_term(st, nrows, nnz, b);
   return QP_OK;
 }
 
@@ -457,47 +365,43 @@ int launch_spmm_cheby(hipStream_t s, const int64_t* rowptr, const int32_t* cols,
                       const double2* X, int64_t nrows, int64_t nnz, int b, const ChebyEpi& e, const Tuning& tun,
                       bool rows_kernel, const int32_t* order, Stats* st) {
   if (nrows == 0) return QP_OK;
-  if (rows_kernel) {
-    const bool nt = spmm_streams_nt(tun, nrows, b);
-#define QP_SPMM_ROWS(RW)                                                                                         \
-  {                                                                                                              \
-    const int64_t per_wg = (int64_t)(kThreads / 64) * RW;                                                        \
-    dim3 grid((unsigned)((nrows + per_wg - 1) / per_wg), (unsigned)((b + 63) / 64));                             \
-    if (nt) {                                                                                                    \
-      ChebyOpT<true> op{e};                                                                                      \
-      hipLaunchKernelGGL((spmm_rows_kernel<ChebyOpT<true>, RW, 8>), grid, dim3(kThreads), 0, s, rowptr, cols, vals, X, nrows, b, op, order); \
-    } else {                                                                                                     \
-      ChebyOp op{e};                                                                                             \
-      hipLaunchKernelGGL((spmm_rows_kernel<ChebyOp, RW, 8>), grid, dim3(kThreads), 0, s, rowptr, cols, vals, X, nrows, b, op, order); \
-    }                                                                                                            \
-  }
-    if (tun.spmm_rw <= 0 && nnz <= (int64_t)INT32_MAX) {   // (the scalar-entry kernel broadcasts a 32-bit row pointer)
-      if (nt) {
-        ChebyOpT<true> op{e};
-        launch_rows_smem(s, rowptr, cols, vals, X, nrows, b, op, order);
-      } else {
-        ChebyOp op{e};
-        launch_rows_smem(s, rowptr, cols, vals, X, nrows, b, op, order);
+  with_cheby_op(e, spmm_streams_nt(tun, nrows, b), [&](auto op) -> int {
+    using Op = decltype(op);
+    const unsigned slices = (unsigned)((b + 63) / 64);
+    // csr_spmm_kernel, TS states per pass
+    auto state_tiled = [&](auto ts) {
+      constexpr int TS = decltype(ts)::value, rpw = kThreads / TS;
+      dim3 grid((unsigned)((nrows + rpw - 1) / rpw), (unsigned)((b + TS - 1) / TS));
+      hipLaunchKernelGGL((csr_spmm_kernel<Op, TS>), grid, dim3(kThreads), 0, s, rowptr, cols, vals, X, nrows, b, op);
+    };
+    // spmm_rows_kernel, RW rows per wavefront
+    auto rows = [&](auto rw) {
+      constexpr int RW = decltype(rw)::value;
+      const int64_t per_wg = (int64_t)(kThreads / 64) * RW;
+      hipLaunchKernelGGL((spmm_rows_kernel<Op, RW>), dim3((unsigned)((nrows + per_wg - 1) / per_wg), slices), dim3(kThreads), 0, s, rowptr,
+                         cols, vals, X, nrows, b, op, order);
+    };
+    if (!rows_kernel) {
+      // states per pass of the tiled kernel: 16 (the gather window of a banded H stays inside an XCD's L2; 32 and 64 measured slower,
+      // profiles/r02/batched_c5_sweep.txt); a panel of at most eight states (one GPU's share of 64 over 8): 8, no idle lanes
+      if (b <= 8) state_tiled(std::integral_constant<int, 8>{});
+      else state_tiled(std::integral_constant<int, 16>{});
+    } else if (tun.spmm_rw <= 0 && nnz <= (int64_t)INT32_MAX) {   // (the scalar-entry kernel broadcasts a 32-bit row pointer)
+      constexpr int WS = 8;
+      hipLaunchKernelGGL((spmm_rows_smem_kernel<Op, WS>), dim3((unsigned)((nrows + WS - 1) / WS), slices), dim3(64 * WS), 0, s, rowptr,
+                         cols, vals, X, nrows, b, op, order);
+    } else {
+      switch (tun.spmm_rw) {
+        case 2: rows(std::integral_constant<int, 2>{}); break;
+        case 4: rows(std::integral_constant<int, 4>{}); break;
+        case 8: rows(std::integral_constant<int, 8>{}); break;
+        default: rows(std::integral_constant<int, 1>{}); break;
       }
-    } else
-    switch (tun.spmm_rw) {
-      case 2: QP_SPMM_ROWS(2) break;
-      case 4: QP_SPMM_ROWS(4) break;
-      case 8: QP_SPMM_ROWS(8) break;
-      default: QP_SPMM_ROWS(1) break;
     }
-#undef QP_SPMM_ROWS
-  } else
-  // states per pass of the tiled kernel: 16 (the gather window of a banded H stays inside an XCD's L2; 32 and 64 measured slower,
-  // profiles/r02/batched_c5_sweep.txt); a panel of at most eight states (one GPU's share of 64 over 8): 8, no idle lanes
-  if (b <= 8) launch_spmm_cheby_t<8>(s, rowptr, cols, vals, X, nrows, b, e, tun.spmm_nt);
-  else launch_spmm_cheby_t<16>(s, rowptr, cols, vals, X, nrows, b, e, tun.spmm_nt);
+    return QP_OK;
+  });
   QP_HIP(hipGetLastError());
-  if (st) {
-    st->n_launch++;
-    st->n_matvec++;
-    st->spmv_bytes += 20.0 * (double)nnz + 4.0 * (double)(nrows + 1) + 80.0 * (double)nrows * b;
-  }
+  count_panel_term(st, nrows, nnz, b);
   return QP_OK;
 }
 

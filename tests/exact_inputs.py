@@ -1,5 +1,5 @@
 """Exact inputs and output digests for the tests that hold a build's bits against digests recorded from an earlier build
-(tests/test_gpu_zgemm_bits.py, tests/test_gpu_rowblock_bits.py): 31-bit integers of a quadratic integer recurrence modulo a
+(tests/test_gpu_zgemm_bits.py, tests/test_gpu_rowblock_bits.py, tests/test_gpu_panel_bits.py): 31-bit integers of a quadratic integer recurrence modulo a
 prime, scaled by a power of two -- no random-number library, so a digest depends on the kernels alone.  The product of two such
 values does not fit a double: every accumulate rounds, and a wrong operand or summation order changes the digest."""
 import hashlib
