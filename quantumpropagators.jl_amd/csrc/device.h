@@ -80,13 +80,7 @@ struct DevMatrix {
 // (tile t, block c) lists the entries of the tile's rows whose column lies in block c, row by row, columns ascending.  The
 // kernel walks the column blocks in the OUTER loop -- every wavefront is resident from the start and owns its tiles for the
 // whole launch -- so at any time the whole chip gathers from one 2^log2w-element window of x that every XCD's L2 holds.
-struct ColBlockPlan {
-  int valid = 0;
-  int log2w = 17;               // columns per block = 1 << log2w  (2 MB of x)
-  int P = 0;                    // column blocks
-  int rpt = 2;                  // 64-row groups per tile
-  int max_seg = 0;              // entries of the longest segment (the per-wavefront LDS buffer holds one segment)
-  int64_t ntiles = 0, nnz = 0;
+struct ColBlockPlan : ColBlockShape {   // (layout_constants.h: the numbers the planner decides)
   int32_t* segptr = nullptr;    // device [ntiles P + 1]: first entry of segment t P + c
   uint16_t* rowoff = nullptr;   // device [ntiles P (64 rpt + 1)]: first entry of every row inside its segment
   uint32_t* cols = nullptr;     // device [nnz]
@@ -116,8 +110,6 @@ struct CodedVals {
   double* tab_r = nullptr;        // device [ntab]: its real parts, read instead when every value is real
   int use_real = 0;
 };
-constexpr int kCbMaxTilesPerWave = 8;
-constexpr int kCbMaxSeg = 1024;
 
 // epilogue of the fused Chebyshev term (see qp_cheby_term in qprop.h)
 struct ChebyEpi {
@@ -242,11 +234,9 @@ inline int dense_gemv_grid(int64_t nrows) {
 // Developer knobs for A/B measurements.  Every context carries its own copy (qp_ctx::tun, set with
 // qp_ctx_tuning_set); qp_tuning_set only changes the defaults that contexts created afterwards start
 // from, so handles driven from different threads never observe each other's switches.
-// fixed choices that were knobs while they were being measured (docs/history/): the density from which AUTO lays an operator out dense,
-// the resident wavefronts per CU the column-blocked mirror is sized for (24 and 32 measured slower)
+// a fixed choice that was a knob while it was being measured (docs/history/): the density from which AUTO lays an operator out dense
+// (the column-blocked mirror's: layout_constants.h)
 constexpr int kDenseMinDensityPct = 75;
-constexpr int kCbWavesPerCu = 16;
-constexpr int kCbMinLog2N = 20;     // column-blocked mirror: smallest number of columns (log2) it is built for (measured: 2^18 columns 0.9 x, 2^19 1.04 x, 2^20 1.37 x, 2^21 1.62 x, 2^22 1.52 x)
 
 struct Tuning {
   int rbcsr_variant = 15;     // bit 0 nt matrix loads, bit 1 early row-local loads, bit 2 deeper unroll, bit 3 (Hermitian-packed kernel) all loads of an all-stencil block up front (A/B in profiles/)
@@ -318,17 +308,7 @@ int launch_spmm_cheby(hipStream_t s, const int64_t* rowptr, const int32_t* cols,
 // in LDS (one KiB per row: 64 states) and its sixteen wavefronts, one per row as in the row kernel, take their operands from
 // there.  What decides the speed of the row kernel is the bytes it pulls out of L2 (17-21 KiB per row at the L2's ~18 TB/s:
 // tools/probe/panel_tile_probe.hip, profiles/r06/panel_tile_probe.txt); the tile pulls 5 + the row-local streams.
-constexpr int kSpmmTileMaxEntries = 24;   // entries per row (2 K + 2 NN + 1 = 17 at most; a multiple of 8: the sums go in groups of eight)
-constexpr int kSpmmTileSlots = 80;        // staged rows at most (K = NN = 4): 80 KiB of LDS, two workgroups per compute unit
-struct SpmmTileShape {
-  int nd = 0, K = 0, NN = 0;
-  int dfar[kSpmmTileMaxEntries] = {0};    // entry k: strip steps m (d = m g) when dnear[k] == 0 ...
-  int dnear[kSpmmTileMaxEntries] = {0};   // ... else the near distance d
-};
-// the kernel's table (device, int32): [0, 80) row of staged slot s relative to the tile's first row r0; then for wavefront w = 4 i + j
-// and entry k the LDS byte offset of that entry's operand (24 per wavefront); then the wavefront's own row relative to r0 (16) and
-// the LDS byte offset of its own element (16)
-constexpr int kSpmmTileTab = kSpmmTileSlots + 16 * kSpmmTileMaxEntries + 32;
+// (SpmmTileShape, the kSpmmTile* sizes and the layout of the kernel's table: layout_constants.h)
 struct SpmmTiles {
   bool built = false;
   int valid = 0;

@@ -1,6 +1,6 @@
 // Operators of the C ABI (the lazy sum of include/qprop.h): creation, the device build, evaluate! (operator_refresh), the
 // *_info getters and qp_operator_get_csr.  A thin device layer: WHAT the arrays hold is computed by the pure-host layout unit
-// (operator_layout.h) and by the planners of engine_plans.hip; this file uploads the results, phase by phase.
+// (operator_layout.h) and by the pure-host planning unit (operator_plans.h, through engine_plans.hip); this file uploads the results, phase by phase.
 #include <atomic>
 
 #include "engine_host.h"
@@ -355,7 +355,7 @@ int qp_operator_create(qp_ctx* ctx, qp_matrix* const* ops, int nops, int ncoeffs
   qp::HostVec<int32_t> uc_orig;
   if (!dense && (format == QP_FMT_AUTO || format == QP_FMT_HRB)) {
     const int64_t before = ur[nrows];
-    lattice_fill(ctx->tun, nrows, ncols, ur, uc, &ur_orig, &uc_orig);      // (ur_orig / uc_orig stay empty when nothing was completed)
+    lattice_fill(plan_knobs(ctx->tun), nrows, ncols, ur, uc, &ur_orig, &uc_orig);      // (ur_orig / uc_orig stay empty when nothing was completed)
     op->n_lattice_fill = ur[nrows] - before;
     if (op->n_lattice_fill == 0) {
       ur_orig.clear();
@@ -602,10 +602,10 @@ int qp_lattice_fill_host(int64_t nrows, int64_t ncols, const int64_t* rowptr, co
     return qp::fail(QP_E_BAD_ARG, "qp_lattice_fill_host: bad arguments");
   qp::HostVec<int64_t> ur(rowptr, rowptr + nrows + 1);
   qp::HostVec<int32_t> uc(col, col + rowptr[nrows]);
-  qp::Tuning tun;
-  tun.lattice_fill = 1;
-  tun.walk_min_blocks = min_blocks;
-  lattice_fill(tun, nrows, ncols, ur, uc);
+  PlanKnobs knobs;
+  knobs.lattice_fill = 1;
+  knobs.walk_min_blocks = min_blocks;
+  lattice_fill(knobs, nrows, ncols, ur, uc);
   *nnz_out = ur[nrows];
   if (ur[nrows] > cap) return qp::fail(QP_E_BAD_ARG, "qp_lattice_fill_host: col_out holds %lld entries, %lld needed", (long long)cap, (long long)ur[nrows]);
   std::memcpy(rowptr_out, ur.data(), ur.size() * sizeof(int64_t));

@@ -337,7 +337,7 @@ def lattice_fill_host(nrows, ncols, rowptr, col, min_blocks=3072):
     """The lattice completion of operator creation on a host CSR pattern (no device needed): returns (rowptr, col)."""
     rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
     col = np.ascontiguousarray(col, dtype=np.int32)
-    # the completion adds the missing entries of the rows (up to 12 %, engine_plans.hip: lattice_fill) plus the transposes that land
+    # the completion adds the missing entries of the rows (up to 12 %, operator_plans.cpp: lattice_fill) plus the transposes that land
     # in the first and last `reach` rows -- bounded by the pattern, not by a constant: ask for the size first (a call with no room
     # reports the count it needs), then fill
     rp_out = np.empty(nrows + 1, dtype=np.int64)

@@ -2,8 +2,8 @@
 // host before a kernel ever runs -- union pattern, Hermitian check, format choice, lattice completion, strip-walk plan, column
 // encodings (int32 / int16 / stencil / block map), Hermitian packing with transposed positions, column-blocked mirror, value
 // dictionary -- and the decoders of qp_operator_get_csr, compiled from the library's own sources (csrc/engine_core.hip,
-// csrc/engine_operator.hip, csrc/engine_plans.hip here; csrc/operator_layout.cpp, csrc/walk_geometry.cpp and csrc/host_numerics.cpp beside it as
-// ordinary C++) with g++ against tests/hip_host_shim (device memory = heap memory, so the
+// csrc/engine_operator.hip, csrc/engine_plans.hip here; csrc/operator_layout.cpp, csrc/operator_plans.cpp, csrc/walk_geometry.cpp and
+// csrc/host_numerics.cpp beside it as ordinary C++) with g++ against tests/hip_host_shim (device memory = heap memory, so the
 // sanitizer checks every copy into a "device" array against its allocation) and driven by a fuzz over the shapes that have bitten:
 // tall (5681 x 358: the round-4 GPU memory fault), wide, 1 row, fewer than 64 rows, empty rows, lattices, grids, spin chains.
 // Checked per case: the get_csr round trip reproduces the input exactly; EVERY stored slot of every row block -- real entries,
@@ -13,10 +13,14 @@
 // swept over chip sizes and knobs and checked against the kernels' own segment formulas: every strip step belongs to exactly one
 // segment, every edge block is reached, the launch fits the chip; and a table of named inputs (tests/walk_geometry_cases.h) pins
 // the numbers.
+// The plans themselves (csrc/operator_plans.cpp, the pure-host unit engine_plans.hip uploads from): the batched path's row order, tiles
+// and LDS operand table are checked BY CONSTRUCTION over every knob value (permutation, partition, every operand slot names the
+// entry's column); every verdict of the walk's shape parser and the whole plans of named operators are pinned by
+// tests/operator_plan_cases.h (`--print-plan-cases` prints that table's rows from the tree it is built against).
 // Built and run by tests/test_cabi_host.py::test_host_index_work_under_sanitizers (CPU only).
 // `--digest`: per case one line with the format, the scalar fields of the layout structs and a 64-bit FNV-1a hash over the
 // declared extent of every "device" array the operator owns -- two builds of the library lay operators out bit-identically iff
-// their outputs agree.  For this mode build WITHOUT the sanitizers and with -DQP_SHIM_ZERO_ALLOC (bytes the build never writes
+// their outputs agree; the lazily built plans of the batched path (row order at 8 and 64 states, tiles, operand table) included.  For this mode build WITHOUT the sanitizers and with -DQP_SHIM_ZERO_ALLOC (bytes the build never writes
 // then compare equal).  The values depend on the standard library's distributions: compare, do not store.
 #include <cstdio>
 #include <random>
@@ -25,6 +29,7 @@
 #include "../quantumpropagators.jl_amd/csrc/engine_operator.hip"
 #include "../quantumpropagators.jl_amd/csrc/engine_plans.hip"
 #include "walk_geometry_cases.h"
+#include "operator_plan_cases.h"
 
 // ---- host stand-ins of the few launches the creation path makes (values only; no kernel runs in this build) ---------------
 namespace qp {
@@ -131,7 +136,7 @@ int64_t n_cases = 0, n_walked = 0, n_hrb = 0, n_coded = 0, n_cb = 0, n_dense = 0
 bool g_digest = false;
 
 // --digest: see the head of this file
-void print_digest(const qp_operator* op, const char* what) {
+void print_digest(qp_operator* op, const char* what) {
   uint64_t h = 1469598103934665603ull;
   auto bytes = [&](const void* p, size_t n) {
     for (size_t i = 0; i < n; ++i) h = (h ^ static_cast<const unsigned char*>(p)[i]) * 1099511628211ull;
@@ -186,6 +191,27 @@ void print_digest(const qp_operator* op, const char* what) {
     bytes(C.codes, (size_t)A.stored);
     bytes(C.tptr, nb * 8);
     for (const double2* p : op->cv_tplanes) bytes(p, (size_t)C.ntab * 16);
+  }
+  if (A.format != QP_FMT_MATFREE) {   // the batched path's plans, built at the first batched step
+    for (int batch : {8, 64}) {
+      const int32_t* order = nullptr;
+      if (operator_spmm_order(op, batch, &order) != QP_OK) std::abort();
+      for (long long v : {(long long)(order != nullptr), (long long)op->m_order_g, (long long)op->m_order_sw}) num(v);
+      if (order) bytes(order, (size_t)A.nrows * 4);
+    }
+    const qp::SpmmTiles* T = nullptr;
+    if (operator_spmm_tiles(op, &T) != QP_OK) std::abort();
+    const qp::SpmmTiles& M = op->m_tiles;
+    for (long long v : {(long long)M.valid, (long long)M.ntiles, (long long)M.nrest, (long long)M.g, (long long)M.sw, (long long)M.T, (long long)M.shape.nd,
+                        (long long)M.shape.K, (long long)M.shape.NN})
+      num(v);
+    bytes(M.shape.dfar, sizeof M.shape.dfar);
+    bytes(M.shape.dnear, sizeof M.shape.dnear);
+    if (T) {
+      bytes(T->tiles, (size_t)T->ntiles * 4);
+      bytes(T->rest, (size_t)T->nrest * 4);
+      bytes(T->tab, (size_t)qp::kSpmmTileTab * 4);
+    }
   }
   std::printf("digest %s | format %d |%s | %016llx\n", what, A.format, scalars.c_str(), (unsigned long long)h);
 }
@@ -571,10 +597,374 @@ Csr tfim(int n) {
   return out;
 }
 
+// ---- generators without a standard-library distribution (their operators' plans are pinned in tests/operator_plan_cases.h) ------
+struct Lcg {
+  uint64_t s;
+  uint32_t next() {
+    s = s * 6364136223846793005ull + 1442695040888963407ull;
+    return (uint32_t)(s >> 33);
+  }
+};
+// up to `maxlen` entries per row at columns drawn by the generator above (value 1)
+Csr lcg_csr(uint64_t seed, int64_t nrows, int64_t ncols, int minlen, int maxlen) {
+  Lcg g{seed};
+  Csr out;
+  out.nrows = nrows;
+  out.ncols = ncols;
+  out.rp.assign((size_t)nrows + 1, 0);
+  std::vector<int32_t> row;
+  for (int64_t r = 0; r < nrows; ++r) {
+    row.clear();
+    const int len = minlen + (int)(g.next() % (uint32_t)(maxlen - minlen + 1));
+    for (int k = 0; k < len; ++k) row.push_back((int32_t)(g.next() % (uint64_t)ncols));
+    std::sort(row.begin(), row.end());
+    row.erase(std::unique(row.begin(), row.end()), row.end());
+    for (int32_t c : row) {
+      out.col.push_back(c);
+      out.val.push_back(qp_c128{1.0, 0.0});
+    }
+    out.rp[(size_t)r + 1] = (int64_t)out.col.size();
+  }
+  return out;
+}
+// five-point stencil on an nx x ny grid with open boundaries, row = y nx + x
+Csr open_grid(int64_t nx, int64_t ny) {
+  Csr out;
+  out.nrows = out.ncols = nx * ny;
+  out.rp.assign((size_t)(nx * ny) + 1, 0);
+  for (int64_t y = 0; y < ny; ++y)
+    for (int64_t x = 0; x < nx; ++x) {
+      const int64_t r = y * nx + x;
+      auto put = [&](int64_t c, double v) {
+        out.col.push_back((int32_t)c);
+        out.val.push_back(qp_c128{v, 0.0});
+      };
+      if (y > 0) put(r - nx, -1.0);
+      if (x > 0) put(r - 1, -1.0);
+      put(r, 4.0);
+      if (x + 1 < nx) put(r + 1, -1.0);
+      if (y + 1 < ny) put(r + nx, -1.0);
+      out.rp[(size_t)r + 1] = (int64_t)out.col.size();
+    }
+  return out;
+}
+Csr const_lattice(int64_t N, const std::vector<int64_t>& dist, bool periodic = true) {
+  std::mt19937_64 unused(1);   // (constant values: the generator draws nothing)
+  return lattice(unused, N, dist, periodic, true);
+}
+
+struct Pattern {   // a Csr's pattern as the planners take it
+  UnionRowptr ur;
+  UnionCols uc;
+  int64_t nrows, ncols;
+  explicit Pattern(const Csr& c) : ur(c.rp.begin(), c.rp.end()), uc(c.col.begin(), c.col.end()), nrows(c.nrows), ncols(c.ncols) {}
+  UnionPattern view() const { return UnionPattern{nrows, ncols, ur, uc}; }
+};
+
+// ---- the batched path's plans, checked by construction (csrc/operator_plans.cpp: plan_spmm_order, plan_spmm_tiles, spmm_tile_table) ----
+int64_t n_panel_orders = 0, n_panel_tiles = 0, n_panel_operands = 0;
+// want_order / want_tiles: must SOME knob setting take the plan (1), must none (0)
+void check_panel_plans(const Csr& csr, const char* what, int want_order, int want_tiles, int want_rest = -1, int want_T = 0) {
+  const Pattern pat(csr);
+  const UnionPattern A = pat.view();
+  const int64_t n = A.nrows;
+  int got_order = 0, got_tiles = 0;
+  for (int knob : {-1, 0, 8, 64}) {
+    for (int batch : {1, 8, 64, 130}) {
+      const SpmmOrder O = plan_spmm_order(A, batch, knob);
+      if (O.order.empty()) {
+        REQUIRE(O.g == 0 && O.sw == 0, "%s: no row order but g %lld sw %lld", what, (long long)O.g, (long long)O.sw);
+        continue;
+      }
+      got_order = 1;
+      ++n_panel_orders;
+      REQUIRE((int64_t)O.order.size() == n && O.g >= 256 && O.sw >= 1 && O.sw < O.g && O.g % O.sw == 0, "%s: row order of %zu rows, g %lld sw %lld", what,
+              O.order.size(), (long long)O.g, (long long)O.sw);
+      std::vector<char> seen((size_t)n, 0);
+      for (int32_t r : O.order) {
+        REQUIRE(r >= 0 && r < n && !seen[(size_t)r], "%s (strip %d, batch %d): row %d twice in the order, or outside the matrix", what, knob, batch, r);
+        seen[(size_t)r] = 1;
+      }
+    }
+    const SpmmTilesHost P = plan_spmm_tiles(A, knob);
+    if (P.tiles.empty()) {
+      REQUIRE(P.rest.empty() && P.g == 0 && P.sw == 0 && P.shape.nd == 0, "%s: an empty tile plan carries data", what);
+      continue;
+    }
+    got_tiles = 1;
+    ++n_panel_tiles;
+    const qp::SpmmTileShape& sh = P.shape;
+    const int64_t g = P.g;
+    REQUIRE(16 * (int64_t)P.tiles.size() >= n / 2, "%s: %zu tiles cover less than half of %lld rows", what, P.tiles.size(), (long long)n);
+    REQUIRE(g >= 64 && sh.nd >= 2 && sh.nd <= qp::kSpmmTileMaxEntries && sh.K >= 1 && sh.K <= 4 && sh.NN >= 0 && sh.NN <= 4, "%s: tile shape", what);
+    std::vector<int64_t> D((size_t)sh.nd);   // the candidate distance list
+    for (int k = 0; k < sh.nd; ++k) D[(size_t)k] = sh.dnear[k] != 0 ? (int64_t)sh.dnear[k] : (int64_t)sh.dfar[k] * g;
+    std::vector<char> owner((size_t)n, 0);
+    for (int32_t r0 : P.tiles)
+      for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+          const int64_t r = (int64_t)r0 + i * g + j;
+          REQUIRE(r0 >= 0 && r < n, "%s: tile %d row %lld outside the matrix", what, r0, (long long)r);
+          REQUIRE(!owner[(size_t)r], "%s: row %lld in two tiles", what, (long long)r);
+          owner[(size_t)r] = 1;
+          REQUIRE(A.ur[r + 1] - A.ur[r] == sh.nd, "%s: tile row %lld has %lld entries, the candidate %d", what, (long long)r, (long long)(A.ur[r + 1] - A.ur[r]), sh.nd);
+          for (int k = 0; k < sh.nd; ++k)
+            REQUIRE((int64_t)A.uc[A.ur[r] + k] - r == D[(size_t)k], "%s: entry %d of tile row %lld is not at distance %lld", what, k, (long long)r, (long long)D[(size_t)k]);
+        }
+    for (int32_t r : P.rest) {
+      REQUIRE(r >= 0 && r < n && !owner[(size_t)r], "%s: rest row %d is in a tile, listed twice or outside the matrix", what, r);
+      owner[(size_t)r] = 1;
+    }
+    for (int64_t r = 0; r < n; ++r) REQUIRE(owner[(size_t)r], "%s: row %lld in neither a tile nor the rest", what, (long long)r);
+    if (want_rest >= 0) REQUIRE((int)!P.rest.empty() == want_rest, "%s: %zu rest rows", what, P.rest.size());
+    // the kernel's table (csrc/kernels_spmm.hip, spmm_tile_kernel: LDS byte offset tab[80 + 24 w + k] of wavefront w's entry k)
+    const SpmmTileTable T = spmm_tile_table(sh, g);
+    const std::vector<int32_t>& tab = T.tab;
+    REQUIRE(T.T == 16 + 8 * sh.K + 8 * sh.NN && T.T <= qp::kSpmmTileSlots && (int)tab.size() == qp::kSpmmTileTab, "%s: T %d", what, T.T);
+    if (want_T) REQUIRE(T.T == want_T, "%s: T %d, expected %d", what, T.T, want_T);
+    for (int a = 0; a < T.T; ++a)
+      for (int b = a + 1; b < T.T; ++b) REQUIRE(tab[(size_t)a] != tab[(size_t)b], "%s: staged slots %d and %d hold the same row %d", what, a, b, tab[(size_t)a]);
+    const int base = qp::kSpmmTileSlots, per = qp::kSpmmTileMaxEntries;
+    for (int w = 0; w < 16; ++w) {
+      const int64_t own_row = (int64_t)(w / 4) * g + w % 4;
+      for (int k = 0; k < sh.nd; ++k) {
+        const int32_t off = tab[(size_t)(base + per * w + k)];
+        REQUIRE(off >= 0 && off % 1024 == 0 && off < T.T * 1024, "%s: operand offset %d of wavefront %d entry %d", what, off, w, k);
+        REQUIRE((int64_t)tab[(size_t)(off / 1024)] == own_row + D[(size_t)k], "%s: wavefront %d entry %d reads staged row %d, its column is row + %lld", what, w, k,
+                tab[(size_t)(off / 1024)], (long long)(own_row + D[(size_t)k]));
+        ++n_panel_operands;
+      }
+      REQUIRE((int64_t)tab[(size_t)(base + per * 16 + w)] == own_row, "%s: own row of wavefront %d", what, w);
+      const int32_t own_off = tab[(size_t)(base + per * 16 + 16 + w)];
+      REQUIRE(own_off >= 0 && own_off % 1024 == 0 && own_off < T.T * 1024 && (int64_t)tab[(size_t)(own_off / 1024)] == own_row, "%s: own-row offset %d of wavefront %d", what, own_off, w);
+    }
+  }
+  REQUIRE(want_order < 0 || got_order == want_order, "%s: row order taken %d, expected %d", what, got_order, want_order);
+  REQUIRE(want_tiles < 0 || got_tiles == want_tiles, "%s: tiles taken %d, expected %d", what, got_tiles, want_tiles);
+}
+
+// the open-boundary grid as the operator build completes it
+Csr completed(const Csr& c, int min_blocks) {
+  Pattern p(c);
+  PlanKnobs k;
+  k.walk_min_blocks = min_blocks;
+  lattice_fill(k, p.nrows, p.ncols, p.ur, p.uc);
+  REQUIRE((int64_t)p.uc.size() > (int64_t)c.col.size(), "lattice_fill left the %lld x %lld open grid as it was", (long long)c.nrows, (long long)c.ncols);
+  Csr out;
+  out.nrows = c.nrows;
+  out.ncols = c.ncols;
+  out.rp.assign(p.ur.begin(), p.ur.end());
+  out.col.assign(p.uc.begin(), p.uc.end());
+  out.val.assign(out.col.size(), qp_c128{0.0, 0.0});
+  return out;
+}
+
+void check_panel_plan_cases() {
+  std::mt19937_64 rng(7);
+  for (const auto& st : std::vector<std::vector<int64_t>>{{1, 2, 3, 4, 64, 128, 192, 256}, {1, 64}, {1, 2, 100, 200}, {1, 63, 64, 65}, {1, 32, 1024}, {3, 17}, {20, 40}})
+    for (int64_t N : {(int64_t)4096, (int64_t)5000, (int64_t)16384 + 77})
+      for (int periodic = 0; periodic < 2; ++periodic) check_panel_plans(lattice(rng, N, st, periodic != 0, false), "lattice generator", -1, -1);
+  check_panel_plans(const_lattice(4096, {1, 64}), "64 x 64 periodic grid", 0, 1);
+  check_panel_plans(const_lattice(4096, {1, 256}), "256 x 16 periodic grid", 1, 1);
+  check_panel_plans(completed(open_grid(96, 64), 16), "open 96 x 64 grid, completed", 0, 1, 1);
+  check_panel_plans(const_lattice((int64_t)1 << 15, {1, 2, 3, 4, 1024, 2048, 3072, 4096}), "(4,4) lattice, g = 1024", 1, 1);
+  check_panel_plans(const_lattice(4096, {1, 2, 3, 4, 64, 128, 192, 256}), "K = NN = 4 at g = 64", 0, 1, -1, qp::kSpmmTileSlots);
+  check_panel_plans(tfim(12), "spin chain", 0, 0);
+  check_panel_plans(lcg_csr(11, 4096, 4096, 0, 11), "ragged operator", 0, 0);
+  std::printf("panel plans: %lld row orders are permutations, %lld tile plans partition their rows, %lld LDS operands name their entry's column\n",
+              (long long)n_panel_orders, (long long)n_panel_tiles, (long long)n_panel_operands);
+}
+
+// ---- every verdict of the walk's shape parser (tests/operator_plan_cases.h) ------------------------------------------------------
+std::string c_string(const std::string& s) {
+  std::string out = "\"";
+  for (char c : s) {
+    if (c == '"' || c == '\\') out += '\\';
+    out += c;
+  }
+  return out + "\"";
+}
+void check_shape_table(bool print) {
+  int n_ok = 0, n_refused = 0;
+  for (const ShapeCase& c : kShapeCases) {
+    const std::vector<int64_t> dl(c.d, c.d + c.n);
+    WalkShape w;
+    std::string text;
+    const int code = walk_shape_reason(dl, w, &text);
+    if (code != QP_WALK_OK) w = WalkShape();
+    (code == QP_WALK_OK ? n_ok : n_refused)++;
+    if (print) {
+      std::printf("  {%s, %d, {", c_string(c.name).c_str(), c.n);
+      for (int k = 0; k < c.n; ++k) std::printf("%s%lld", k ? "," : "", c.d[k]);
+      std::printf("}, %d, %s, %d,%d,%d,%d,%d, %lld,%lld,%lld, {%d,%d,%d,%d}},\n", code, c_string(text).c_str(), w.nn, w.K, w.z0, w.xl, w.fd, (long long)w.g,
+                  (long long)w.glong, (long long)w.glong1, w.near[0], w.near[1], w.near[2], w.near[3]);
+      continue;
+    }
+    REQUIRE(code == c.code && text == c.text, "shape table, %s: code %d \"%s\", expected %d \"%s\"", c.name, code, text.c_str(), c.code, c.text);
+    REQUIRE(parse_walk_shape(dl, w) == (c.code == QP_WALK_OK), "shape table, %s: parse_walk_shape", c.name);
+    if (code != QP_WALK_OK) continue;
+    REQUIRE(w.nn == c.nn && w.K == c.K && w.z0 == c.z0 && w.xl == c.xl && w.fd == c.fd && w.g == c.g && w.glong == c.glong && w.glong1 == c.glong1 &&
+                w.near[0] == c.near[0] && w.near[1] == c.near[1] && w.near[2] == c.near[2] && w.near[3] == c.near[3],
+            "shape table, %s: nn %d K %d z0 %d xl %d fd %d g %lld glong %lld glong1 %lld near %d %d %d %d", c.name, w.nn, w.K, w.z0, w.xl, w.fd, (long long)w.g,
+            (long long)w.glong, (long long)w.glong1, w.near[0], w.near[1], w.near[2], w.near[3]);
+  }
+  if (!print) std::printf("walk shapes: %d accepted and %d refused distance lists match the table\n", n_ok, n_refused);
+}
+
+// ---- named operators -> whole plans (tests/operator_plan_cases.h) ------------------------------------------------------------------
+struct PlanInput {
+  const char* name;
+  Csr (*make)();
+  int format;
+  std::vector<std::pair<const char*, int>> knobs;
+  bool sweep_cu;   // also at 8 and 64 compute units (the column-blocked mirror's tiles-per-wavefront gate reads the count)
+};
+const PlanInput kPlanInputs[] = {
+    {"(4,4) lattice g 64, N 4096", [] { return const_lattice(4096, {1, 2, 3, 4, 64, 128, 192, 256}); }, QP_FMT_AUTO, {{"walk_min_blocks", 8}}, false},
+    {"(1,1) lattice g 64, N 5000, open ends", [] { return const_lattice(5000, {1, 64}, false); }, QP_FMT_AUTO, {{"walk_min_blocks", 8}}, false},
+    {"(2,2) lattice g 100, N 16461", [] { return const_lattice(16461, {1, 2, 100, 200}); }, QP_FMT_AUTO, {{"walk_min_blocks", 8}}, false},
+    {"nine-point lattice g 64, N 16461", [] { return const_lattice(16461, {1, 63, 64, 65}); }, QP_FMT_AUTO, {{"walk_min_blocks", 8}}, false},
+    {"nine-point lattice g 65, N 16461", [] { return const_lattice(16461, {1, 64, 65, 66}); }, QP_FMT_AUTO, {{"walk_min_blocks", 8}}, false},
+    {"near distance 32, N 4096, packed", [] { return const_lattice(4096, {1, 32, 1024}); }, QP_FMT_HRB, {{"walk_min_blocks", 8}}, false},
+    {"band of five, N 4096, packed", [] { return const_lattice(4096, {1, 2, 3, 4, 5}); }, QP_FMT_HRB, {{"walk_min_blocks", 8}}, false},
+    {"(4,4) lattice g 1024, N 2^15", [] { return const_lattice((int64_t)1 << 15, {1, 2, 3, 4, 1024, 2048, 3072, 4096}); }, QP_FMT_AUTO, {{"walk_min_blocks", 8}}, false},
+    {"chain of blocks g 64, N 2048", [] { return const_lattice(2048, {1, 64}); }, QP_FMT_AUTO, {{"walk_min_blocks", 8}}, false},
+    {"64 x 64 periodic grid", [] { return const_lattice(4096, {1, 64}); }, QP_FMT_AUTO, {{"walk_min_blocks", 8}}, false},
+    {"256 x 16 periodic grid", [] { return const_lattice(4096, {1, 256}); }, QP_FMT_AUTO, {{"walk_min_blocks", 8}}, false},
+    {"256 x 16 periodic grid, strips of 8", [] { return const_lattice(4096, {1, 256}); }, QP_FMT_AUTO, {{"walk_min_blocks", 8}, {"spmm_strip", 8}}, false},
+    {"open 96 x 64 grid", [] { return open_grid(96, 64); }, QP_FMT_AUTO, {{"walk_min_blocks", 8}}, false},
+    {"open 96 x 64 grid, default knobs", [] { return open_grid(96, 64); }, QP_FMT_AUTO, {}, false},
+    {"12-spin chain", [] { return tfim(12); }, QP_FMT_AUTO, {}, false},
+    {"12-spin chain, packed", [] { return tfim(12); }, QP_FMT_HRB, {}, false},
+    {"ragged 4096 x 4096", [] { return lcg_csr(11, 4096, 4096, 0, 11); }, QP_FMT_RBCSR, {}, false},
+    {"random columns N 4096, mirror forced", [] { return lcg_csr(12, 4096, 4096, 8, 8); }, QP_FMT_RBCSR, {{"colblock", 2}, {"cb_log2w", 6}}, true},
+    {"random columns N 4096, mirror forced, CSR", [] { return lcg_csr(12, 4096, 4096, 8, 8); }, QP_FMT_CSR, {{"colblock", 2}, {"cb_log2w", 6}}, true},
+    {"random columns N 2^18, mirror forced", [] { return lcg_csr(13, (int64_t)1 << 18, (int64_t)1 << 18, 2, 2); }, QP_FMT_RBCSR, {{"colblock", 2}, {"cb_log2w", 12}}, true},
+    {"long pair 16384, N 2^16: walkable decides", [] { return const_lattice((int64_t)1 << 16, {1, 64, 16384}); }, QP_FMT_AUTO, {{"walk_min_blocks", 8}}, false},
+    {"long pair 16384, N 2^16: walk off", [] { return const_lattice((int64_t)1 << 16, {1, 64, 16384}); }, QP_FMT_AUTO, {{"walk_min_blocks", 8}, {"hrb_walk", 0}}, false},
+};
+
+struct PlanRecord {
+  long long s[kPlanScalars];
+  double line_share;
+  unsigned long long h[kPlanHashes];
+  std::string text;
+};
+uint64_t fnv(const void* p, size_t n) {
+  uint64_t h = 1469598103934665603ull;
+  for (size_t i = 0; i < n; ++i) h = (h ^ static_cast<const unsigned char*>(p)[i]) * 1099511628211ull;
+  return h;
+}
+// s: format, n_lattice_fill, walk reason | one-term plan, two-term plan: valid nn K z0 S xl glong glong1 fd g R0 R1 W0 U0 ustride n_edge
+// near[0..3] | mirror: valid log2w P rpt max_seg ntiles nnz | row order at 64 states: g sw | tiles: valid ntiles nrest g sw T nd K NN
+// h: edge lists of the two plans | mirror: segptr rowoff cols map | row order | tiles, rest, table
+PlanRecord plan_record(qp_operator* op) {
+  PlanRecord R{};
+  int i = 0;
+  auto put = [&](long long v) { R.s[i++] = v; };
+  put(op->A.format), put(op->n_lattice_fill), put(op->walk_reason);
+  R.text = op->walk_reason_text;
+  int hi = 0;
+  for (const qp::WalkPlan* P : {&op->walk, &op->walk2}) {
+    for (long long v : {(long long)P->valid, (long long)P->nn, (long long)P->K, (long long)P->z0, (long long)P->S, (long long)P->xl, (long long)P->glong,
+                        (long long)P->glong1, (long long)P->fd, (long long)P->g, (long long)P->R0, (long long)P->R1, (long long)P->W0, (long long)P->U0,
+                        (long long)P->ustride, (long long)P->n_edge})
+      put(v);
+    for (int k = 0; k < 4; ++k) put(P->near[k]);
+    R.h[hi++] = P->valid ? fnv(P->edge_map, (size_t)P->n_edge * 4) : 0;
+  }
+  const qp::ColBlockPlan& B = op->cb;
+  for (long long v : {(long long)B.valid, (long long)B.log2w, (long long)B.P, (long long)B.rpt, (long long)B.max_seg, (long long)B.ntiles, (long long)B.nnz}) put(v);
+  R.line_share = op->cb_line_share;
+  R.h[hi++] = B.valid ? fnv(B.segptr, (size_t)(B.ntiles * B.P + 1) * 4) : 0;
+  R.h[hi++] = B.valid ? fnv(B.rowoff, (size_t)(B.ntiles * B.P) * (size_t)(64 * B.rpt + 1) * 2) : 0;
+  R.h[hi++] = B.valid ? fnv(B.cols, (size_t)B.nnz * 4) : 0;
+  R.h[hi++] = B.valid ? fnv(B.map, (size_t)B.nnz * 8) : 0;
+  const int32_t* order = nullptr;
+  REQUIRE(operator_spmm_order(op, 64, &order) == QP_OK, "operator_spmm_order");
+  put(op->m_order_g), put(op->m_order_sw);
+  R.h[hi++] = order ? fnv(order, (size_t)op->A.nrows * 4) : 0;
+  const qp::SpmmTiles* T = nullptr;
+  REQUIRE(operator_spmm_tiles(op, &T) == QP_OK, "operator_spmm_tiles");
+  const qp::SpmmTiles& M = op->m_tiles;
+  for (long long v : {(long long)M.valid, (long long)M.ntiles, (long long)M.nrest, (long long)M.g, (long long)M.sw, (long long)M.T, (long long)M.shape.nd,
+                      (long long)M.shape.K, (long long)M.shape.NN})
+    put(v);
+  R.h[hi++] = T ? fnv(T->tiles, (size_t)T->ntiles * 4) : 0;
+  R.h[hi++] = T ? fnv(T->rest, (size_t)T->nrest * 4) : 0;
+  R.h[hi++] = T ? fnv(T->tab, (size_t)qp::kSpmmTileTab * 4) : 0;
+  REQUIRE(i == kPlanScalars && hi == kPlanHashes, "plan record: %d scalars, %d hashes", i, hi);
+  return R;
+}
+// the mirror's part of the record on a chip of `cu` compute units: the planner itself, on the operator's pattern and layout
+void colblock_record(const qp_operator* op, int cu, PlanRecord& R) {
+  const ColBlockHost C = plan_colblock(union_pattern_of(op), op->layout, plan_knobs(op->ctx->tun), cu);
+  const qp::ColBlockShape& B = C.shape;
+  int i = 43;
+  for (long long v : {(long long)B.valid, (long long)B.log2w, (long long)B.P, (long long)B.rpt, (long long)B.max_seg, (long long)B.ntiles, (long long)B.nnz}) R.s[i++] = v;
+  if (C.line_share >= 0.0) R.line_share = C.line_share;
+  R.h[2] = B.valid ? fnv(C.segptr.data(), C.segptr.size() * 4) : 0;
+  R.h[3] = B.valid ? fnv(C.rowoff.data(), C.rowoff.size() * 2) : 0;
+  R.h[4] = B.valid ? fnv(C.cols.data(), C.cols.size() * 4) : 0;
+  R.h[5] = B.valid ? fnv(C.map.data(), C.map.size() * 8) : 0;
+}
+
+void check_plan_table(bool print) {
+  int n_rows = 0;
+  for (const PlanInput& in : kPlanInputs) {
+    qp_ctx* ctx = nullptr;
+    REQUIRE(qp_ctx_create(0, nullptr, &ctx) == QP_OK, "qp_ctx_create");
+    for (const auto& kv : in.knobs) REQUIRE(qp_ctx_tuning_set(ctx, kv.first, kv.second) == QP_OK, "knob %s", kv.first);
+    const Csr t = in.make();
+    qp_matrix* m = nullptr;
+    std::vector<int64_t> idx(t.col.begin(), t.col.end());
+    REQUIRE(qp_matrix_create(ctx, t.nrows, t.ncols, (int64_t)t.col.size(), t.rp.data(), idx.data(), t.val.data(), QP_VAL_C128, QP_LAYOUT_CSR, 0, QP_FMT_AUTO, &m) == QP_OK,
+            "%s: qp_matrix_create", in.name);
+    qp_operator* op = nullptr;
+    REQUIRE(qp_operator_create(ctx, &m, 1, 0, in.format, &op) == QP_OK, "%s: qp_operator_create: %s", in.name, qp::g_last_error.c_str());
+    const PlanRecord built = plan_record(op);
+    for (int cu : {256, 64, 8}) {
+      if (cu != 256 && !in.sweep_cu) continue;
+      PlanRecord R = built;
+      colblock_record(op, cu, R);
+      if (cu == 256) {   // the build asked the (stand-in) device, which has 256
+        REQUIRE(std::memcmp(R.s, built.s, sizeof R.s) == 0 && std::memcmp(R.h, built.h, sizeof R.h) == 0 && R.line_share == built.line_share,
+                "%s: the planner and the built operator disagree about the column-blocked mirror", in.name);
+      }
+      ++n_rows;
+      if (print) {
+        std::printf("  {%s, %d, {", c_string(in.name).c_str(), cu);
+        for (int k = 0; k < kPlanScalars; ++k) std::printf("%s%lld", k ? "," : "", R.s[k]);
+        std::printf("}, %a, {", R.line_share);
+        for (int k = 0; k < kPlanHashes; ++k) std::printf("%s0x%016llxull", k ? "," : "", R.h[k]);
+        std::printf("}, %s},\n", c_string(R.text).c_str());
+        continue;
+      }
+      const PlanCase* want = nullptr;
+      for (const PlanCase& c : kPlanCases)
+        if (std::strcmp(c.name, in.name) == 0 && c.cu == cu) want = &c;
+      REQUIRE(want, "plan table: no row for %s at %d compute units", in.name, cu);
+      for (int k = 0; k < kPlanScalars; ++k) REQUIRE(R.s[k] == want->s[k], "plan table, %s at %d CUs: scalar %d is %lld, expected %lld", in.name, cu, k, R.s[k], want->s[k]);
+      for (int k = 0; k < kPlanHashes; ++k) REQUIRE(R.h[k] == want->h[k], "plan table, %s at %d CUs: hash %d is %016llx, expected %016llx", in.name, cu, k, R.h[k], want->h[k]);
+      REQUIRE(R.line_share == want->line_share && R.text == want->text, "plan table, %s at %d CUs: line share %a, reason \"%s\"", in.name, cu, R.line_share, R.text.c_str());
+    }
+    if (g_digest) print_digest(op, in.name);
+    qp_operator_destroy(op);
+    qp_matrix_destroy(m);
+    qp_ctx_destroy(ctx);
+  }
+  if (!print) std::printf("operator plans: %d rows of named operators match the table\n", n_rows);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   g_digest = argc > 1 && std::strcmp(argv[1], "--digest") == 0;
+  if (argc > 1 && std::strcmp(argv[1], "--print-plan-cases") == 0) {   // the rows of tests/operator_plan_cases.h
+    check_shape_table(true);
+    check_plan_table(true);
+    return 0;
+  }
   qp_ctx* ctx = nullptr;
   if (qp_ctx_create(0, nullptr, &ctx) != QP_OK) {
     std::fprintf(stderr, "qp_ctx_create: %s\n", qp::g_last_error.c_str());
@@ -660,6 +1050,9 @@ int main(int argc, char** argv) {
     check_operator(ctx, terms, 0, rep % 3 == 0 ? QP_FMT_CSR : QP_FMT_RBCSR, "forced column-blocked mirror");
   }
   check_cut_table();
+  check_panel_plan_cases();
+  check_shape_table(false);
+  check_plan_table(false);
   std::printf("walk geometry: %lld cuts of %lld one-term and %lld two-term plans keep every strip step in exactly one segment\n", (long long)n_cuts,
               (long long)n_walked, (long long)n_walk2);
   qp_ctx_destroy(ctx);

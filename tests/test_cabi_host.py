@@ -244,7 +244,7 @@ def test_partition_rows_bit_exact():
 
 @pytest.mark.parametrize("nx,ny,nnn", [(100, 60, False), (64, 90, False), (130, 50, True), (70, 400, False)])
 def test_lattice_fill_host_completes_open_boundary_grids(nx, ny, nnn):
-    """Index work of the lattice completion (engine_plans.hip: lattice_fill, the host half of qp_operator_create), bit-exact
+    """Index work of the lattice completion (operator_plans.cpp: lattice_fill, the host half of qp_operator_create), bit-exact
     against a NumPy restatement: every row between the first and the last grid row of an open-boundary grid Hamiltonian
     gets the full distance list of the stencil (explicit zeros where the grid's x-edge cut a neighbour off), the entries
     that land in the first / last grid row get their transposes, nothing else changes."""
@@ -450,29 +450,31 @@ def test_host_numerics_under_sanitizers(tmp_path):
 def test_host_index_work_under_sanitizers(tmp_path):
     """the HOST INDEX WORK of operator creation -- format choice, lattice completion, strip-walk plan, column
     encodings, Hermitian packing, column-blocked mirror, value dictionary, the get_csr decoders -- compiled from the library's own
-    sources (csrc/engine_core.hip, engine_operator.hip, engine_plans.hip, operator_layout.cpp, host_numerics.cpp) with g++ -fsanitize=address,undefined against a host
+    sources (csrc/engine_core.hip, engine_operator.hip, engine_plans.hip, operator_layout.cpp, operator_plans.cpp, host_numerics.cpp) with g++ -fsanitize=address,undefined against a host
     stand-in of the HIP runtime (tests/hip_host_shim: device memory = heap memory, so every copy into a "device" array is
     bounds-checked) and fuzzed over tall / wide / 1-row / N < 64 / empty-row shapes, lattices and spin chains
     (tests/sanitize_host_index.cpp; the 5681 x 358 operator of the round-4 GPU memory fault is the first case).  Every stored slot
     -- pads and the lanes beyond the last row included -- must decode to a column inside the matrix, every pad must be zero.
-    The layout unit (csrc/operator_layout.cpp), the launch geometry of the strip walks (csrc/walk_geometry.cpp) and the plan of the
+    The layout unit (csrc/operator_layout.cpp), the planning unit (csrc/operator_plans.cpp), the launch geometry of the strip walks (csrc/walk_geometry.cpp) and the plan of the
     persistent small-system kernels (csrc/small_plan.cpp) must stay pure host
     code: they compile without the HIP stand-in on the include path.  For every operator with a strip-walk plan the harness sweeps the
     cut of its launches over chip sizes and knobs against the kernels' own segment formulas (every strip step in exactly one
-    segment, every edge block reached, the launch fits the chip) and checks a table of named inputs (tests/walk_geometry_cases.h)."""
+    segment, every edge block reached, the launch fits the chip) and checks a table of named inputs (tests/walk_geometry_cases.h).
+    The plans of the batched path (row order, LDS tiles, the tile kernel's operand table) are checked by construction over every
+    knob value, and every verdict of the walk's shape parser and the whole plans of named operators against tests/operator_plan_cases.h."""
     import shutil
     import subprocess
     if shutil.which("g++") is None:
         pytest.skip("g++ not available")
     csrc = os.path.join(ROOT, "quantumpropagators.jl_amd", "csrc")
     exe = str(tmp_path / "host_index_san")
-    for unit in ("operator_layout.cpp", "walk_geometry.cpp", "small_plan.cpp"):
+    for unit in ("operator_layout.cpp", "operator_plans.cpp", "walk_geometry.cpp", "small_plan.cpp"):
         pure = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", csrc, os.path.join(csrc, unit)], capture_output=True, text=True)
         assert pure.returncode == 0, pure.stderr[-3000:]
     build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-x", "c++",
                             "-I", os.path.join(ROOT, "tests", "hip_host_shim"), "-I", csrc,
                             os.path.join(ROOT, "tests", "sanitize_host_index.cpp"), os.path.join(csrc, "host_numerics.cpp"),
-                            os.path.join(csrc, "operator_layout.cpp"), os.path.join(csrc, "walk_geometry.cpp"),
+                            os.path.join(csrc, "operator_layout.cpp"), os.path.join(csrc, "operator_plans.cpp"), os.path.join(csrc, "walk_geometry.cpp"),
                             "-o", exe, "-lpthread"], capture_output=True, text=True)
     if build.returncode != 0 and "sanitize" in build.stderr and "cannot find" in build.stderr:
         pytest.skip("sanitizer runtime not installed")
@@ -488,3 +490,10 @@ def test_host_index_work_under_sanitizers(tmp_path):
     assert geo and int(geo.group(2)) == n["with a strip-walk plan"] and int(geo.group(3)) >= 1 and int(geo.group(1)) >= 100 * int(geo.group(2))
     cases = __import__("re").search(r"walk geometry: (\d+) named cases .* match the table", run.stdout)
     assert cases and int(cases.group(1)) >= 12
+    # the planning unit: panel plans by construction, the shape parser's verdicts and the named operators' plans against their table
+    panel = __import__("re").search(r"panel plans: (\d+) row orders are permutations, (\d+) tile plans partition their rows, (\d+) LDS operands", run.stdout)
+    assert panel and int(panel.group(1)) >= 20 and int(panel.group(2)) >= 20 and int(panel.group(3)) >= 16 * 5 * int(panel.group(2)), run.stdout[-2000:]
+    shapes = __import__("re").search(r"walk shapes: (\d+) accepted and (\d+) refused distance lists match the table", run.stdout)
+    assert shapes and int(shapes.group(1)) >= 11 and int(shapes.group(2)) >= 13
+    plans = __import__("re").search(r"operator plans: (\d+) rows of named operators match the table", run.stdout)
+    assert plans and int(plans.group(1)) >= 28
