@@ -626,7 +626,8 @@ int qp_cheby_term_split(qp_operator* op, qp_split* sp, void* boundary_stream, in
   qp_ctx* ctx = op->ctx;
   QP_CHECK(use(ctx));
   hipStream_t S_c = ctx->stream, S_x = (hipStream_t)boundary_stream;
-  qp::RowSet rb{sp->bmap_boundary, sp->n_boundary, false};
+  // (the term is counted as ONE mat-vec: by its interior launch, or by the boundary launch where there is no interior block)
+  qp::RowSet rb{sp->bmap_boundary, sp->n_boundary, sp->n_interior == 0};
   qp::RowSet ri{sp->bmap_interior, sp->n_interior, true};
   if (sp->walk.valid) {   // lattice operator: the interior as a strip walk; CUs beyond the edge workgroups' stay free (knob) for
     ri.walk = &sp->walk;  // the boundary launch and the collective's kernel that run beside it

@@ -34,6 +34,16 @@ XOFFS = (0, 64, G)
 C, BETA, A_PREV, A, A_D1, A_D2 = 0.7 - 1.3j, -0.9, 1.7, -0.6, 2.3, -1.4
 PH_UNIT, PH_NONUNIT = complex(np.exp(-0.7j)), 0.6 - 1.1j
 
+# the guard zones of the GPU tests (tests/test_gpu_cheby_term.py: Guarded; tests/split_term_cases.py: check_slab)
+GUARD = 256
+SENTINEL = complex(-7.25e33, 3.5e-21)
+JUNK = complex(4.5e-9, -8.75e17)          # what an output vector holds before the call
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a, dtype=np.complex128), np.ascontiguousarray(b, dtype=np.complex128)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
 
 @dataclasses.dataclass(frozen=True)
 class Form:

@@ -41,13 +41,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import qprop_amd.lib as L  # noqa: E402
 import cheby_term_ref as R  # noqa: E402
 import cheby_term_cases as cases  # noqa: E402
-from cheby_term_cases import A, A_PREV, BETA, C  # noqa: E402
+from cheby_term_cases import A, A_PREV, BETA, C, GUARD, JUNK, SENTINEL, same_bits  # noqa: E402
 from test_gpu_rowblock_bits import knobs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-GUARD = 256
-SENTINEL = complex(-7.25e33, 3.5e-21)
-JUNK = complex(4.5e-9, -8.75e17)          # what an output vector holds before the call
 
 
 @pytest.fixture(scope="module")
@@ -55,11 +52,6 @@ def ctx():
     c = L.Context(0)
     yield c
     c.close()
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.complex128), np.ascontiguousarray(b, dtype=np.complex128)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
 class Guarded:
