@@ -5,9 +5,12 @@
 #pragma once
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
+#include <new>
 #include <system_error>
 #include <thread>
 
@@ -78,30 +81,58 @@ struct BuildTrace {
   }
 };
 
-// rows [0, n) in contiguous chunks on a few host threads (index work whose iterations write disjoint positions)
+// The threaded-build harness (tests/sanitize_host_index.cpp --large, built with -DQP_PARALLEL_ROWS_TRACE) learns which call
+// sites of parallel_rows really started threads: every call then carries its caller's file and line.  Without the macro nothing
+// of this exists.
+#ifdef QP_PARALLEL_ROWS_TRACE
+void qp_parallel_rows_threaded(const char* file, int line, size_t nthreads);   // (the harness defines it)
+#define QP_PARALLEL_ROWS_SITE , const char* site_file = __builtin_FILE(), int site_line = __builtin_LINE()
+#else
+#define QP_PARALLEL_ROWS_SITE
+#endif
+
+// rows [0, n) in contiguous chunks on a few host threads (index work whose iterations write disjoint positions).  A chunk that
+// throws (std::bad_alloc of a worker's scratch vector) does not end the process: every thread is joined, and the first
+// exception is rethrown on the calling thread, where the C ABI's QP_CATCH makes a status of it as it does on the serial path.
 template <class F>
-inline void parallel_rows(int64_t n, F&& fn, int64_t serial_below = (int64_t)1 << 16) {
+inline void parallel_rows(int64_t n, F&& fn, int64_t serial_below = (int64_t)1 << 16 QP_PARALLEL_ROWS_SITE) {
   const unsigned hw = host_threads();
   if (n < serial_below || hw == 1) {
     fn((int64_t)0, n);
     return;
   }
+  std::exception_ptr err;
+  std::atomic<bool> failed{false};
+  auto guarded = [&fn, &err, &failed](int64_t a, int64_t b) {
+    try {
+      fn(a, b);
+    } catch (...) {
+      if (!failed.exchange(true)) err = std::current_exception();   // (read after the joins)
+    }
+  };
   std::vector<std::thread> th;
+  th.reserve(hw);
   const int64_t chunk = (n + hw - 1) / hw;
   int64_t done = 0;   // rows [0, done) have been handed to a thread
   try {
     for (unsigned t = 0; t < hw; ++t) {
       const int64_t a = (int64_t)t * chunk, b = std::min(n, a + chunk);
       if (a >= b) break;
-      th.emplace_back([&fn, a, b] { fn(a, b); });
+      th.emplace_back([&guarded, a, b] { guarded(a, b); });
       done = b;
     }
   } catch (const std::system_error&) {
     // no more threads to be had (resource limits): the started ones are joined below -- a joinable std::thread destroyed
     // means std::terminate -- and this thread takes the rest
+  } catch (const std::bad_alloc&) {
+    // (nor memory for a thread's start record: the same)
   }
+#ifdef QP_PARALLEL_ROWS_TRACE
+  if (th.size() >= 2) qp_parallel_rows_threaded(site_file, site_line, th.size());
+#endif
   for (auto& x : th) x.join();
-  if (done < n) fn(done, n);
+  if (done < n) guarded(done, n);
+  if (err) std::rethrow_exception(err);
 }
 
 // dst[0, n) = src[0, n) on the host threads (gigabyte arrays: one thread's memcpy is a third of the machine's rate)

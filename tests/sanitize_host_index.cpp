@@ -22,14 +22,50 @@
 // declared extent of every "device" array the operator owns -- two builds of the library lay operators out bit-identically iff
 // their outputs agree; the lazily built plans of the batched path (row order at 8 and 64 states, tiles, operand table) included.  For this mode build WITHOUT the sanitizers and with -DQP_SHIM_ZERO_ALLOC (bytes the build never writes
 // then compare equal).  The values depend on the standard library's distributions: compare, do not store.
+// `--large`: the THREADED host build -- a fixed list of operators of 2^16 .. 2^18 rows that crosses every serial threshold of
+// parallel_rows, with the digests, the call sites that really started threads, the error paths at size and the throwing-worker
+// checks (tests/test_cabi_host.py::test_threaded_host_build: equal digests at every thread count, ThreadSanitizer, ASan/UBSan).
+#include <atomic>
 #include <cstdio>
+#include <mutex>
+#include <new>
 #include <random>
+#include <set>
+#include <thread>
 
 #include "../quantumpropagators.jl_amd/csrc/engine_core.hip"
 #include "../quantumpropagators.jl_amd/csrc/engine_operator.hip"
 #include "../quantumpropagators.jl_amd/csrc/engine_plans.hip"
 #include "walk_geometry_cases.h"
 #include "operator_plan_cases.h"
+
+// ---- the call sites of parallel_rows that started at least two threads (csrc/operator_layout.h, QP_PARALLEL_ROWS_TRACE) -----
+namespace {
+std::mutex g_sites_lock;
+std::set<std::pair<std::string, int>> g_sites;
+}  // namespace
+void qp_parallel_rows_threaded(const char* file, int line, size_t) {
+  const char* base = std::strrchr(file, '/');
+  std::lock_guard<std::mutex> hold(g_sites_lock);
+  g_sites.insert({base ? base + 1 : file, line});
+}
+
+// ---- out of memory on a worker thread, on demand (uninstrumented builds: the sanitizers bring an operator new of their own) ----
+#if !defined(__SANITIZE_ADDRESS__) && !defined(__SANITIZE_THREAD__)
+#define QP_HARNESS_OWN_NEW 1
+namespace {
+std::atomic<int> g_new_failures{0};   // so many allocations made off the main thread fail
+std::thread::id g_main_thread = std::this_thread::get_id();
+}  // namespace
+void* operator new(size_t n) {
+  if (g_new_failures.load(std::memory_order_relaxed) > 0 && std::this_thread::get_id() != g_main_thread && g_new_failures.fetch_sub(1) > 0)
+    throw std::bad_alloc();
+  if (void* p = std::malloc(n ? n : 1)) return p;
+  throw std::bad_alloc();
+}
+void operator delete(void* p) noexcept { std::free(p); }
+void operator delete(void* p, size_t) noexcept { std::free(p); }
+#endif
 
 // ---- host stand-ins of the few launches the creation path makes (values only; no kernel runs in this build) ---------------
 namespace qp {
@@ -358,12 +394,38 @@ void check_cut_table() {
   std::printf("walk geometry: %d named cases (%d one-term, %d two-term) match the table\n", n_one + n_two, n_one, n_two);
 }
 
-void check_operator(qp_ctx* ctx, const std::vector<Csr>& terms, int ncoeffs, int format, const char* what) {
+// how the terms reach qp_matrix_create (--large): the index base, real values as QP_VAL_F64, and `raw` -- the arrays really passed
+// in, whose canonical form (columns ascending, repeated columns summed) the terms are
+struct InputForm {
+  int index_base = 0;
+  bool f64 = false;
+  const std::vector<Csr>* raw = nullptr;
+};
+struct Features {   // of the operator check_operator built last (--large prints and requires them)
+  int built = 0, format = 0, walk = 0, walk2 = 0, cv = 0, cb = 0, sparse_from = -1, planes_real = 0;
+  long long n_lattice_fill = 0, cb_tiles = 0, stored = 0, lstored = 0, nblocks = 0, relayouts = 0;
+} g_last;
+bool g_large = false;
+
+void check_operator(qp_ctx* ctx, const std::vector<Csr>& terms, int ncoeffs, int format, const char* what, const InputForm& in = InputForm()) {
   std::vector<qp_matrix*> ms;
-  for (const Csr& t : terms) {
+  g_last = Features();
+  for (size_t l = 0; l < terms.size(); ++l) {
+    const Csr& t = in.raw ? (*in.raw)[l] : terms[l];
     qp_matrix* m = nullptr;
-    std::vector<int64_t> idx(t.col.begin(), t.col.end());
-    REQUIRE(qp_matrix_create(ctx, t.nrows, t.ncols, (int64_t)t.col.size(), t.rp.data(), idx.data(), t.val.data(), QP_VAL_C128, QP_LAYOUT_CSR, 0, QP_FMT_AUTO, &m) == QP_OK,
+    std::vector<int64_t> idx(t.col.size()), rp(t.rp.size());
+    for (size_t p = 0; p < idx.size(); ++p) idx[p] = (int64_t)t.col[p] + in.index_base;
+    for (size_t r = 0; r < rp.size(); ++r) rp[r] = t.rp[r] + in.index_base;
+    std::vector<double> re;
+    if (in.f64) {
+      re.resize(t.val.size());
+      for (size_t p = 0; p < re.size(); ++p) {
+        REQUIRE(t.val[p].im == 0.0, "%s: QP_VAL_F64 input wants real values", what);
+        re[p] = t.val[p].re;
+      }
+    }
+    REQUIRE(qp_matrix_create(ctx, t.nrows, t.ncols, (int64_t)t.col.size(), rp.data(), idx.data(), in.f64 ? (const void*)re.data() : (const void*)t.val.data(),
+                             in.f64 ? QP_VAL_F64 : QP_VAL_C128, QP_LAYOUT_CSR, in.index_base, QP_FMT_AUTO, &m) == QP_OK,
             "%s: qp_matrix_create: %s", what, qp::g_last_error.c_str());
     ms.push_back(m);
   }
@@ -382,6 +444,14 @@ void check_operator(qp_ctx* ctx, const std::vector<Csr>& terms, int ncoeffs, int
   if (op->cv.valid) ++n_coded;
   if (op->cb.valid) ++n_cb;
   if (g_digest) print_digest(op, what);
+  g_last.built = 1, g_last.format = A.format, g_last.walk = op->walk.valid, g_last.walk2 = op->walk2.valid, g_last.cv = op->cv.valid, g_last.cb = op->cb.valid;
+  g_last.sparse_from = op->sparse_from, g_last.planes_real = op->planes_real, g_last.n_lattice_fill = op->n_lattice_fill;
+  g_last.cb_tiles = op->cb.valid ? (long long)op->cb.ntiles : 0, g_last.stored = A.stored, g_last.lstored = A.lstored, g_last.nblocks = A.nblocks;
+  if (g_large)
+    std::printf("features %s | format %d walk.valid %d walk2.valid %d n_lattice_fill %lld cv.valid %d cb.valid %d (tiles %lld) sparse_from %d planes_real %d | "
+                "rows %lld blocks %lld stored %lld lower %lld\n",
+                what, g_last.format, g_last.walk, g_last.walk2, g_last.n_lattice_fill, g_last.cv, g_last.cb, g_last.cb_tiles, g_last.sparse_from, g_last.planes_real,
+                (long long)nrows, g_last.nblocks, g_last.stored, g_last.lstored);
   // ---- round trip: one term, unit coefficient -> the input bit for bit (more terms: the union pattern, values summed)
   {
     const int64_t nnz = A.nnz;
@@ -475,6 +545,11 @@ void check_operator(qp_ctx* ctx, const std::vector<Csr>& terms, int ncoeffs, int
     for (int rep = 0; rep < 3; ++rep) {
       for (int i = 0; i < ncoeffs; ++i) c[(size_t)i] = qp_c128{0.25 * (rep + 1) - i, rep == 2 ? 0.5 : 0.0};
       REQUIRE(qp_operator_set_coeffs(op, c.data(), ncoeffs) == QP_OK, "%s: set_coeffs: %s", what, qp::g_last_error.c_str());
+    }
+    g_last.relayouts = op->n_relayouts;
+    if (g_large) {   // (a complex coefficient has sent a Hermitian-packed operator back to plain row blocks: the second build's arrays)
+      std::printf("features %s, after set_coeffs | format %d relayouts %lld\n", what, A.format, g_last.relayouts);
+      print_digest(op, (std::string(what) + ", after set_coeffs").c_str());
     }
   }
   qp_operator_destroy(op);
@@ -956,6 +1031,254 @@ void check_plan_table(bool print) {
   if (!print) std::printf("operator plans: %d rows of named operators match the table\n", n_rows);
 }
 
+// ---- --large: the threaded host build (head of this file) ---------------------------------------------------------------------------
+// values without a random number generator: binary fractions of a hash of (row, column), conjugate-symmetric, a real diagonal
+qp_c128 arith_value(int64_t r, int64_t c, bool complex_vals) {
+  const int64_t lo = std::min(r, c), hi = std::max(r, c);
+  const uint32_t h = (uint32_t)((uint64_t)lo * 2654435761ull + (uint64_t)hi * 40503ull + 12345ull);
+  const double re = ((double)((h >> 7) % 2001u) - 1000.0) / 1024.0;
+  const double im = (complex_vals && r != c) ? ((double)((h >> 18) % 2001u) - 1000.0) / 1024.0 : 0.0;
+  return qp_c128{re, r <= c ? im : -im};
+}
+Csr with_arith_values(Csr m, bool complex_vals) {
+  for (int64_t r = 0; r < m.nrows; ++r)
+    for (int64_t p = m.rp[(size_t)r]; p < m.rp[(size_t)r + 1]; ++p) m.val[(size_t)p] = arith_value(r, m.col[(size_t)p], complex_vals);
+  return m;
+}
+// k columns per row drawn by the generator of lcg_csr, each with its transpose: a Hermitian operator whose gathers are irregular
+Csr lcg_hermitian(uint64_t seed, int64_t n, int k) {
+  Lcg g{seed};
+  std::vector<std::vector<int32_t>> rows((size_t)n);
+  for (int64_t r = 0; r < n; ++r)
+    for (int j = 0; j < k; ++j) {
+      const int64_t c = (int64_t)(g.next() % (uint64_t)n);
+      if (c == r) continue;
+      rows[(size_t)r].push_back((int32_t)c);
+      rows[(size_t)c].push_back((int32_t)r);
+    }
+  Csr out;
+  out.nrows = out.ncols = n;
+  out.rp.assign((size_t)n + 1, 0);
+  for (int64_t r = 0; r < n; ++r) {
+    auto& row = rows[(size_t)r];
+    std::sort(row.begin(), row.end());
+    row.erase(std::unique(row.begin(), row.end()), row.end());
+    for (int32_t c : row) {
+      out.col.push_back(c);
+      out.val.push_back(qp_c128{0.0, 0.0});
+    }
+    out.rp[(size_t)r + 1] = (int64_t)out.col.size();
+  }
+  return with_arith_values(std::move(out), true);
+}
+// a control term on few positions: the pairs (i, i + 1), (i + 1, i) for every `every`-th row i, value 1/2
+Csr sparse_pairs(int64_t n, int64_t every) {
+  Csr out;
+  out.nrows = out.ncols = n;
+  out.rp.assign((size_t)n + 1, 0);
+  for (int64_t r = 0; r < n; ++r) {
+    int64_t c = -1;
+    if (r % every == 0 && r + 1 < n) c = r + 1;
+    else if (r >= 1 && (r - 1) % every == 0) c = r - 1;
+    if (c >= 0) {
+      out.col.push_back((int32_t)c);
+      out.val.push_back(qp_c128{0.5, 0.0});
+    }
+    out.rp[(size_t)r + 1] = (int64_t)out.col.size();
+  }
+  return out;
+}
+// the same matrix as the caller of a sparse() would pass it: every row's columns descending, and the first entry of every fifth
+// row twice with half the value each (the halves are exact, their sum is the entry)
+Csr scrambled(const Csr& c) {
+  Csr out;
+  out.nrows = c.nrows;
+  out.ncols = c.ncols;
+  out.rp.assign((size_t)c.nrows + 1, 0);
+  for (int64_t r = 0; r < c.nrows; ++r) {
+    const int64_t a = c.rp[(size_t)r], b = c.rp[(size_t)r + 1];
+    const bool twice = r % 5 == 0 && b > a;
+    const qp_c128 half{0.5 * c.val[(size_t)a].re, 0.5 * c.val[(size_t)a].im};
+    if (twice) {
+      out.col.push_back(c.col[(size_t)a]);
+      out.val.push_back(half);
+    }
+    for (int64_t p = b - 1; p >= a; --p) {
+      out.col.push_back(c.col[(size_t)p]);
+      out.val.push_back(twice && p == a ? half : c.val[(size_t)p]);
+    }
+    out.rp[(size_t)r + 1] = (int64_t)out.col.size();
+  }
+  return out;
+}
+
+long long number_after(const std::string& text, const char* key) {
+  const size_t at = text.rfind(key);
+  REQUIRE(at != std::string::npos, "\"%s\" does not say \"%s\"", text.c_str(), key);
+  return std::atoll(text.c_str() + at + std::strlen(key));
+}
+// refusals at size: two bad entries in different chunks of the threaded pass, whichever thread names one must name a bad one
+void check_errors_at_size(qp_ctx* ctx) {
+  const Csr t = const_lattice(((int64_t)1 << 16) + 192, {1, 64});
+  const int64_t n = t.nrows, nnz = (int64_t)t.col.size(), b1 = 1000, b2 = n - 1000;
+  std::vector<int64_t> idx(t.col.begin(), t.col.end());
+  qp_matrix* m = nullptr;
+  {
+    std::vector<int64_t> rp = t.rp;   // rows b1 and b2 end before they begin; every other row stays monotone
+    rp[(size_t)b1 + 1] = rp[(size_t)b1] - 1;
+    rp[(size_t)b2 + 1] = rp[(size_t)b2] - 1;
+    const int rc = qp_matrix_create(ctx, n, n, nnz, rp.data(), idx.data(), t.val.data(), QP_VAL_C128, QP_LAYOUT_CSR, 0, QP_FMT_AUTO, &m);
+    REQUIRE(rc == QP_E_BAD_ARG && m == nullptr, "non-monotone rowptr at size: status %d", rc);
+    const long long named = number_after(qp::g_last_error, "at row ");
+    REQUIRE(named == b1 || named == b2, "non-monotone rowptr: \"%s\" names row %lld, the bad rows are %lld and %lld", qp::g_last_error.c_str(), named, (long long)b1, (long long)b2);
+    std::printf("error path: rowptr not monotone at rows %lld and %lld of %lld -> QP_E_BAD_ARG naming row %lld\n", (long long)b1, (long long)b2, (long long)n, named);
+  }
+  for (int base = 0; base < 2; ++base) {
+    const int64_t p1 = t.rp[(size_t)b1] + 1, p2 = t.rp[(size_t)b2] + 2;
+    std::vector<int64_t> bad(idx), rp(t.rp);
+    for (auto& v : bad) v += base;
+    for (auto& v : rp) v += base;
+    bad[(size_t)p1] = n + base;   // one past the last column
+    bad[(size_t)p2] = base - 1;   // one before the first
+    const int rc = qp_matrix_create(ctx, n, n, nnz, rp.data(), bad.data(), t.val.data(), QP_VAL_C128, QP_LAYOUT_CSR, base, QP_FMT_AUTO, &m);
+    REQUIRE(rc == QP_E_BAD_ARG && m == nullptr, "column out of range at size (index base %d): status %d", base, rc);
+    const long long named = number_after(qp::g_last_error, "out of range at ");
+    REQUIRE(named == p1 || named == p2, "column out of range: \"%s\" names position %lld, the bad ones are %lld and %lld", qp::g_last_error.c_str(), named, (long long)p1, (long long)p2);
+    std::printf("error path: columns out of range at positions %lld and %lld (index base %d) -> QP_E_BAD_ARG naming position %lld\n", (long long)p1, (long long)p2, base, named);
+  }
+}
+
+// a chunk of parallel_rows that throws: the caller catches the exception -- one, whichever chunk was first -- after every other
+// chunk has run to its end; the process goes on
+void check_throwing_workers() {
+  const unsigned hw = host_threads();
+  if (hw < 2) {
+    std::printf("throwing workers: skipped, one host thread\n");
+    return;
+  }
+  const int64_t n = 1000, chunk = (n + hw - 1) / hw, nchunks = (n + chunk - 1) / chunk;
+  int n_checked = 0;
+  for (const std::vector<int64_t>& bad : std::vector<std::vector<int64_t>>{{0}, {n / 2}, {n - 1}, {0, n - 1}, {0, n / 2, n - 1}}) {
+    std::set<int64_t> bad_chunks;
+    for (int64_t r : bad) bad_chunks.insert(r / chunk);
+    std::atomic<int64_t> completed{0};
+    int caught = 0;
+    try {
+      parallel_rows(n, [&](int64_t a, int64_t b) {
+        for (int64_t r : bad)
+          if (a <= r && r < b) throw std::bad_alloc();
+        completed.fetch_add(1);
+      }, 0);
+    } catch (const std::bad_alloc&) {
+      ++caught;
+    }
+    REQUIRE(caught == 1, "throwing workers: %d exceptions reached the caller of a pass with %zu throwing chunks", caught, bad_chunks.size());
+    REQUIRE(completed.load() == nchunks - (int64_t)bad_chunks.size(), "throwing workers: %lld of %lld chunks ran to their end, %zu threw", (long long)completed.load(),
+            (long long)nchunks, bad_chunks.size());
+    ++n_checked;
+  }
+  std::printf("throwing workers: %d passes of %lld chunks, std::bad_alloc caught by the caller once each, every other chunk joined\n", n_checked, (long long)nchunks);
+}
+
+// the same through the C ABI: a worker's scratch vector (the per-row sort of unsorted input) finds no memory -> QP_E_ALLOC
+void check_worker_out_of_memory(qp_ctx* ctx) {
+#ifdef QP_HARNESS_OWN_NEW
+  if (host_threads() < 2) {
+    std::printf("worker out of memory: skipped, one host thread\n");
+    return;
+  }
+  const Csr raw = scrambled(lcg_csr(21, ((int64_t)1 << 16) + 129, 30011, 6, 8));
+  std::vector<int64_t> idx(raw.col.begin(), raw.col.end());
+  qp_matrix* m = nullptr;
+  g_new_failures.store(1);
+  int rc = qp_matrix_create(ctx, raw.nrows, raw.ncols, (int64_t)raw.col.size(), raw.rp.data(), idx.data(), raw.val.data(), QP_VAL_C128, QP_LAYOUT_CSR, 0, QP_FMT_AUTO, &m);
+  const bool fired = g_new_failures.load() <= 0;
+  g_new_failures.store(0);
+  REQUIRE(fired, "worker out of memory: no allocation was made off the main thread");
+  REQUIRE(rc == QP_E_ALLOC && m == nullptr, "worker out of memory: status %d (%s), expected QP_E_ALLOC", rc, qp::g_last_error.c_str());
+  rc = qp_matrix_create(ctx, raw.nrows, raw.ncols, (int64_t)raw.col.size(), raw.rp.data(), idx.data(), raw.val.data(), QP_VAL_C128, QP_LAYOUT_CSR, 0, QP_FMT_AUTO, &m);
+  REQUIRE(rc == QP_OK && m != nullptr, "worker out of memory: the next qp_matrix_create returned %d (%s)", rc, qp::g_last_error.c_str());
+  qp_matrix_destroy(m);
+  std::printf("worker out of memory: qp_matrix_create returned QP_E_ALLOC, the next one QP_OK\n");
+#else
+  (void)ctx;
+  std::printf("worker out of memory: skipped in a sanitizer build\n");
+#endif
+}
+
+int run_large(const char* only) {
+  g_large = g_digest = true;
+  std::printf("host threads %u\n", host_threads());
+  auto fresh_ctx = [](std::initializer_list<std::pair<const char*, int>> knobs) {
+    qp_ctx* c = nullptr;
+    REQUIRE(qp_ctx_create(0, nullptr, &c) == QP_OK, "qp_ctx_create");
+    for (const auto& kv : knobs) REQUIRE(qp_ctx_tuning_set(c, kv.first, kv.second) == QP_OK, "knob %s", kv.first);
+    return c;
+  };
+  qp_ctx* ctx = fresh_ctx({});
+  const int64_t N18 = ((int64_t)1 << 18) + 77, N16 = ((int64_t)1 << 16) + 192;   // 4098 row blocks; just past the row threshold
+  const std::vector<int64_t> headline{1, 2, 3, 4, 1024, 2048, 3072, 4096};
+  // (`--large NAME`: that part of the list alone; `--large -NAME`: the list without it -- the site list then shows what only it reaches)
+  auto wanted = [&](const char* name) { return !only || (only[0] == '-' ? std::strcmp(only + 1, name) != 0 : std::strcmp(only, name) == 0); };
+#define LARGE_REQUIRE(name, cond) REQUIRE(g_last.built && (cond), "%s: the operator lacks what it is on the list for: " #cond, name)
+  if (wanted("banded")) {   // the headline lattice, complex values: Hermitian-packed with both walk plans, plain row blocks, and as chosen
+    const std::vector<Csr> big{with_arith_values(const_lattice(N18, headline), true)};
+    check_operator(ctx, big, 0, QP_FMT_HRB, "banded lattice 2^18+77, HRB");
+    LARGE_REQUIRE("banded HRB", g_last.format == QP_FMT_HRB && g_last.walk && g_last.walk2 && g_last.nblocks >= 4096 && g_last.stored >= (1 << 20) && g_last.lstored >= (1 << 20));
+    InputForm one_based;
+    one_based.index_base = 1;
+    check_operator(ctx, big, 0, QP_FMT_RBCSR, "banded lattice 2^18+77, RBCSR, index base 1", one_based);
+    LARGE_REQUIRE("banded RBCSR", g_last.format == QP_FMT_RBCSR && g_last.nblocks >= 4096);
+    check_operator(ctx, big, 0, QP_FMT_AUTO, "banded lattice 2^18+77, AUTO");
+    LARGE_REQUIRE("banded AUTO", g_last.format == QP_FMT_HRB && g_last.walk && g_last.walk2);
+  }
+  if (wanted("grid")) {   // five-point open grid: lattice completion; all real, passed as QP_VAL_F64
+    const std::vector<Csr> t{open_grid(512, 520)};
+    InputForm f64;
+    f64.f64 = true;
+    REQUIRE((int64_t)t[0].col.size() >= (1 << 20), "open grid: %zu entries", t[0].col.size());
+    check_operator(ctx, t, 0, QP_FMT_AUTO, "open 512 x 520 grid, QP_VAL_F64", f64);
+    LARGE_REQUIRE("open grid", g_last.n_lattice_fill > 0 && g_last.walk && g_last.planes_real);
+  }
+  if (wanted("mirror")) {   // random columns, Hermitian: the column-blocked mirror (forced: it is chosen from 2^20 columns on), >= 512 tiles
+    qp_ctx* c = fresh_ctx({{"colblock", 2}, {"cb_log2w", 12}});
+    const std::vector<Csr> t{lcg_hermitian(13, (int64_t)1 << 17, 2)};
+    check_operator(c, t, 0, QP_FMT_AUTO, "random columns 2^17, Hermitian, mirror");
+    LARGE_REQUIRE("mirror", g_last.cb && g_last.cb_tiles >= 512);
+    qp_ctx_destroy(c);
+  }
+  if (wanted("tall")) {   // few-valued, tall, rows passed unsorted and with repeated columns: the per-thread sort, the value dictionary
+    const std::vector<Csr> t{lcg_csr(21, ((int64_t)1 << 16) + 129, 30011, 6, 8)}, raw{scrambled(t[0])};
+    InputForm in;
+    in.raw = &raw;
+    check_operator(ctx, t, 0, QP_FMT_AUTO, "few-valued tall 65665 x 30011, unsorted and repeated columns", in);
+    LARGE_REQUIRE("tall", g_last.cv && g_last.format == QP_FMT_RBCSR);
+  }
+  if (wanted("tfim")) {
+    const std::vector<Csr> t{tfim(18)};
+    check_operator(ctx, t, 0, QP_FMT_AUTO, "tfim(18)");
+    LARGE_REQUIRE("tfim(18)", g_last.cv && g_last.planes_real);
+  }
+  if (wanted("terms")) {   // drift + a sparse control term; the complex coefficient of check_operator's third set_coeffs re-lays the packed operator out
+    const std::vector<Csr> t{with_arith_values(const_lattice(N16, headline), true), sparse_pairs(N16, 16)};
+    check_operator(ctx, t, 1, QP_FMT_AUTO, "banded lattice 2^16+192 + sparse control term");
+    LARGE_REQUIRE("two terms", g_last.sparse_from == 1 && g_last.relayouts >= 1);
+  }
+  if (wanted("dense")) {   // a tall dense operator: the completion of the pattern on the host threads
+    const std::vector<Csr> t{lcg_csr(22, ((int64_t)1 << 16) + 5, 3, 1, 3)};
+    check_operator(ctx, t, 0, QP_FMT_DENSE, "dense 65541 x 3");
+    LARGE_REQUIRE("dense", g_last.format == QP_FMT_DENSE && g_last.n_lattice_fill > 0);
+  }
+#undef LARGE_REQUIRE
+  if (wanted("errors")) check_errors_at_size(ctx);
+  if (wanted("throws")) check_throwing_workers();
+  if (wanted("oom")) check_worker_out_of_memory(ctx);
+  qp_ctx_destroy(ctx);
+  for (const auto& s : g_sites) std::printf("threaded site %s:%d\n", s.first.c_str(), s.second);
+  std::printf("large run clean: %lld operators on %u host threads, %zu call sites of parallel_rows started threads\n", (long long)n_cases, host_threads(), g_sites.size());
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -965,6 +1288,7 @@ int main(int argc, char** argv) {
     check_plan_table(true);
     return 0;
   }
+  if (argc > 1 && std::strcmp(argv[1], "--large") == 0) return run_large(argc > 2 ? argv[2] : nullptr);
   qp_ctx* ctx = nullptr;
   if (qp_ctx_create(0, nullptr, &ctx) != QP_OK) {
     std::fprintf(stderr, "qp_ctx_create: %s\n", qp::g_last_error.c_str());
