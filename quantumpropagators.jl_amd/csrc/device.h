@@ -158,7 +158,7 @@ struct RowSet {
   int64_t nmap = 0;
   bool count = true;                   // count this launch as a mat-vec in the stats
   SyncArgs sync;
-  // the same set of blocks as a strip walk (interior launch of a split term; engine_cheby.hip: qp_split_create): a plan
+  // the same set of blocks as a strip walk (interior launch of a split term; cheby_plan.cpp: plan_split, uploaded by qp_split_create): a plan
   // whose walkable run lies inside the set and never reads a row of the complementary set, its edge list = the rest of the
   // set.  Only the edge blocks can depend on the other launch: they wait (sync.wait), the walk itself does not.
   const struct WalkPlan* walk = nullptr;

@@ -12,6 +12,7 @@
 
 #include "device.h"
 #include "operator_layout.h"
+#include "cheby_plan.h"
 
 using qp::cplx;
 using qp::DevMatrix;
@@ -306,34 +307,7 @@ inline int64_t operator_longest_row(const qp_operator* op) {
   for (int64_t r = 0; r < op->A.nrows; ++r) maxrow = std::max<int64_t>(maxrow, op->u_rowptr[r + 1] - op->u_rowptr[r]);
   return maxrow;
 }
-bool cheby_small_fits(const qp_operator* op, qp::SmallPlan* plan);                    // engine_cheby.hip: qp_propagate, method 0
+bool cheby_small_fits(const qp_operator* op, qp::SmallPlan* plan);                    // engine_cheby.hip: qp_propagate, method 0 (the gate itself: cheby_plan.h)
 bool small_sweep_fits(const qp_operator* op, int64_t n, int m, qp::SmallPlan* plan);   // engine_krylov.hip: every arnoldi! of m columns
-// which terms of a cheby! touch the Psi accumulator (include/qprop.h, qp_acc_defer)
-void acc_schedule(const double* a, int n_coeffs, bool defer, qp_acc_defer* out);
+// ---- cheby!: the host's decisions on plain data (schedule, scalars, launch sequence, split partition) are cheby_plan.h ----
 void set_defer(qp::ChebyEpi& e, const qp_acc_defer* d);
-// ---- set-up of a cheby! shared by the single-state, the batched and the row-partitioned step (engine_cheby.hip) ----------
-// @assert abs(dt) ~ abs(wrk.dt)   (isapprox, rtol = sqrt(eps))   src/cheby.jl:157
-bool cheby_dt_matches(double dt, double wrk_dt);
-struct ChebyScalars {   // src/cheby.jl:156, :158-162, :211
-  double beta;
-  cplx c, phase;
-  ChebyScalars(double Delta, double E_min, double dt);
-};
-// which terms touch Psi's accumulator (acc_schedule) and what the next one finds there
-struct ChebyAcc {
-  std::vector<qp_acc_defer> sched;
-  double a0;
-  bool updated = false;   // has any term written the accumulator yet?
-  ChebyAcc(const double* a, int n_coeffs, bool defer) : sched((size_t)n_coeffs - 1), a0(a[0]) { acc_schedule(a, n_coeffs, defer, sched.data()); }
-  struct Term {
-    const qp_acc_defer* defer;
-    double a_prev;   // the coefficient of v_0 while the accumulator has not been written
-    bool acc_in;     // the term reads the accumulator
-  };
-  Term term(int m) {   // term m is issued next
-    const qp_acc_defer& d = sched[(size_t)m - 1];
-    const Term t{&d, updated ? 0.0 : a0, updated && !d.skip};
-    updated = updated || !d.skip;
-    return t;
-  }
-};

@@ -2,32 +2,6 @@
 // and the propagate step loop.
 #include "engine.h"
 
-// terms whose epilogue updates the Psi accumulator: every third one counted from the last
-// (the epilogue of term m holds v_{m-2}, v_{m-1}, v_m of the row).  The first update must
-// still see Psi = v_0, which term 2 overwrites in place, so it is forced to term <= 2.
-void acc_schedule(const double* a, int n_coeffs, bool defer, qp_acc_defer* out) {
-  const int nterms = n_coeffs - 1;
-  std::vector<char> upd((size_t)nterms + 1, defer ? 0 : 1);
-  if (defer) {
-    int m0 = nterms;
-    for (; m0 >= 1; m0 -= 3) upd[m0] = 1;
-    if (m0 + 3 == 3) upd[1] = 1;
-  }
-  int last_upd = 0;
-  for (int m = 1; m <= nterms; ++m) {
-    qp_acc_defer& d = out[m - 1];
-    d = qp_acc_defer{0, 0, 0.0, 0.0};
-    if (upd[m]) {
-      d.n_defer = m - last_upd - 1;
-      d.a_d1 = (d.n_defer >= 1) ? a[m - 1] : 0.0;
-      d.a_d2 = (d.n_defer == 2) ? a[m - 2] : 0.0;
-      last_upd = m;
-    } else {
-      d.skip = 1;
-    }
-  }
-}
-
 int split_timed_out(const qp_split* sp) {
   if (sp && sp->timeout_host && __atomic_load_n(sp->timeout_host, __ATOMIC_RELAXED) != 0)
     return qp::fail(QP_E_INTERNAL, "an interior launch of an earlier term timed out waiting for its boundary launch: "
@@ -42,16 +16,6 @@ void set_defer(qp::ChebyEpi& e, const qp_acc_defer* d) {
   e.a_d1 = d->a_d1;
   e.a_d2 = d->a_d2;
 }
-
-bool cheby_dt_matches(double dt, double wrk_dt) {
-  const double x = std::fabs(dt), y = std::fabs(wrk_dt);
-  return std::fabs(x - y) <= 1.4901161193847656e-08 * std::max(x, y);
-}
-
-ChebyScalars::ChebyScalars(double Delta, double E_min, double dt)
-    : beta((Delta / 2) + E_min),
-      c((dt > 0) ? cplx(0, -2.0) / Delta : cplx(0, 2.0) / Delta),
-      phase(std::exp(cplx(0, -1) * beta * dt)) {}
 
 // the epilogue of one fused term from its operands and scalars; a term that skips the accumulator (defer->skip) carries none
 static qp::ChebyEpi cheby_epi(const double2* xloc, const double2* v0, double2* vout, const double2* acc_in, double2* acc_out,
@@ -98,108 +62,145 @@ static bool walk2_wanted(const qp_operator* op) {
          qp::walk2_wanted(op->walk, op->walk2, qp::walk_matrix(op->A), qp::walk_knobs(tun), qp::device_cu_count());
 }
 
-// the launches of one cheby! call (src/cheby.jl:171-211): n_coeffs - 1 fused mat-vec + term
-// kernels and, when the result does not land in Psi's buffer, one copy.
-// Term vectors: `cur` holds v_{m-1} (gathered by term m), `prev` holds v_{m-2}.  A one-term launch writes v_m over v_{m-2} in
-// place; a two-term launch (terms m and m + 1 in one pass over the matrix values, kernels_walk2.hip) writes v_m and v_{m+1} to two
-// vectors nobody reads meanwhile -- the neighbouring strip columns still gather from `cur` and `prev` -- so a step that takes pairs
-// rotates four vectors (Psi's, bufA, bufC, bufD) instead of two.
+// the launches of one cheby! call (src/cheby.jl:171-211): n_coeffs - 1 fused mat-vec + term kernels in the order and with the
+// vectors ChebySequence (cheby_plan.h) names, and, when the result does not land in Psi's buffer, one copy.
 // `launch_term(x, e)` issues one term: the single-state step's mat-vec kernel, or the panel kernels of the batched step (`panel`:
 // element = (row, state); never in pairs, no check_normalization).
 template <class LaunchTerm>
-static int cheby_step_launches(qp_cheby* w, qp_operator* op, qp_state* psi, const double* a, int n_coeffs, ChebyScalars sc,
+static int cheby_step_launches(qp_cheby* w, qp_operator* op, qp_state* psi, const double* a, int n_coeffs, const ChebyScalars& sc,
                                bool check_normalization, bool panel, LaunchTerm&& launch_term) {
   qp_ctx* ctx = op->ctx;
   const DevMatrix& A = op->A;
-  const int nterms = n_coeffs - 1;
-  double2* P = psi->d;
-  double2* B = w->bufA;
-  double2* ACC = w->acc;
-  double2* result = nullptr;
-  ChebyAcc acc(a, n_coeffs, ctx->tun.acc_defer != 0);
-  bool pairs = !panel && !check_normalization && nterms >= 3 && w->bufC && w->bufD && walk2_wanted(op);   // (qp_cheby_step allocated the two vectors)
-  double2 *cur = P, *prev = nullptr;
-  double2* spare[2] = {w->bufC, w->bufD};      // the two vectors no term of the step is reading
-  // the epilogue of term m, issued next: gathers x, v_{m-2} = v0 -> vout, Psi's accumulator -> acc_out unless the schedule skips it
-  auto epi = [&](int m, const double2* x, const double2* v0, double2* vout, double2* acc_out) {
-    const ChebyAcc::Term t = acc.term(m);
-    return cheby_epi(x, v0, vout, t.acc_in ? ACC : nullptr, acc_out, d2(sc.c), sc.beta, t.a_prev, a[m], d2(sc.phase),
-                     (m == nterms) ? 1 : 0, t.defer);
+  double2* const buf[kChebySlots] = {nullptr, psi->d, w->bufA, w->bufC, w->bufD, w->acc};   // (ChebySlot)
+  auto epi = [&](const ChebyTerm& t) {
+    return cheby_epi(buf[(int)t.x], buf[(int)t.v0], buf[(int)t.vout], buf[(int)t.acc_in], buf[(int)t.acc_out], d2(sc.c * t.c_scale),
+                     sc.beta, t.a_prev, t.a, d2(sc.phase), t.apply_phase, t.defer);
   };
-  for (int m = 1; m <= nterms; ++m) {
-    const bool last = (m == nterms);
-    if (m > 1 && pairs && m + 1 <= nterms && !(acc.sched[m - 1].skip == 0 && acc.sched[m].skip == 0)) {
-      // terms m and m + 1 in one pass over the values: y = v_m -> spare[0], z = v_{m+1} -> spare[1]
-      const bool last2 = (m + 1 == nterms);
-      const bool updated_before = acc.updated;
-      const qp::ChebyEpi e1 = epi(m, cur, prev, spare[0], ACC);
-      const qp::ChebyEpi e2 = epi(m + 1, spare[0], cur, last2 ? nullptr : spare[1], ACC);
+  // (qp_cheby_step allocated the two vectors of a step in pairs)
+  const bool pairs = ChebySequence::pairs_possible(n_coeffs, check_normalization, panel) && w->bufC && w->bufD && walk2_wanted(op);
+  ChebySequence seq(a, n_coeffs, ctx->tun.acc_defer != 0, pairs, check_normalization, panel);
+  ChebyLaunch L;
+  while (seq.next(&L)) {
+    if (L.pair) {
+      // terms m and m + 1 in one pass over the values: y = v_m, z = v_{m+1}
+      const qp::ChebyEpi e1 = epi(L.t[0]), e2 = epi(L.t[1]);
       bool launched = false;
-      {
-        const qp::ScopedRange mv_range(ctx->tun.roctx != 0 || qp::ranges_enabled_by_env(), "matrix-vector product");
-        QP_CHECK(qp::launch_hrb_walk2_cheby(ctx->stream, A, op->walk2, cur, e1, e2, ctx->tun, &launched));
-        if (launched) {
-          // term m + 1 of the blocks outside the two-term region: they read y of their neighbours, which the launch above wrote
-          qp::RowSet rs;
-          rs.block_map = op->walk2.edge_map;
-          rs.nmap = op->walk2.n_edge;
-          rs.count = false;
-          QP_CHECK(qp::launch_spmv_cheby(ctx->stream, A, spare[0], e2, &ctx->stats, &rs));
-          ctx->stats.n_launch++;
-          ctx->stats.n_matvec += 2;
-          ctx->stats.spmv_bytes += 2.0 * (20.0 * (double)A.nnz + 4.0 * (double)(A.nrows + 1) + 80.0 * (double)A.nrows);
-        }
-      }
-      if (launched) {
-        result = ACC;
-        double2* const y = spare[0];
-        double2* const z = spare[1];
-        spare[0] = cur;
-        spare[1] = prev;
-        prev = y;
-        cur = z;
-        ++m;
+      const qp::ScopedRange mv_range(ctx->tun.roctx != 0 || qp::ranges_enabled_by_env(), "matrix-vector product");
+      QP_CHECK(qp::launch_hrb_walk2_cheby(ctx->stream, A, op->walk2, e1.xloc, e1, e2, ctx->tun, &launched));
+      if (!launched) {   // not taken after all (the kernel's LDS opt-in was refused): this and every later term as one-term launches
+        seq.refuse();
         continue;
       }
-      // not taken after all (the kernel's LDS opt-in was refused): this and every later term as one-term launches
-      acc.updated = updated_before;
-      pairs = false;
+      // term m + 1 of the blocks outside the two-term region: they read y of their neighbours, which the launch above wrote
+      qp::RowSet rs;
+      rs.block_map = op->walk2.edge_map;
+      rs.nmap = op->walk2.n_edge;
+      rs.count = false;
+      QP_CHECK(qp::launch_spmv_cheby(ctx->stream, A, e2.xloc, e2, &ctx->stats, &rs));
+      ctx->stats.n_launch++;
+      ctx->stats.n_matvec += 2;
+      ctx->stats.spmv_bytes += 2.0 * (20.0 * (double)A.nnz + 4.0 * (double)(A.nrows + 1) + 80.0 * (double)A.nrows);
+      continue;
     }
-    // m = 1: v0 = Psi; Psi = a1 v0; v1 = c (H v0 - beta v0); Psi += a2 v1     :171-182
-    // m > 1: v2 = c (H v1 - beta v1) + v0 (`prev` holds v0, overwritten in place by v2); Psi += a_i v2; rotate            :186-207
-    double2* const acc_out = (m > 1 && last && cur != P && !pairs) ? P : ACC;  // P may be written only while it is not gathered
-    result = acc_out;
-    qp::ChebyEpi e = epi(m, cur, prev, last ? nullptr : (m == 1 ? B : prev), acc_out);
-    // the reference checks terms i >= 3 only (inside the loop at :186)
-    e.check_partials = (check_normalization && m >= 2) ? w->chk_part : nullptr;
-    QP_CHECK(launch_term(cur, e));
+    qp::ChebyEpi e = epi(L.t[0]);
+    e.check_partials = L.t[0].check ? w->chk_part : nullptr;
+    QP_CHECK(launch_term(e.xloc, e));
     if (e.check_partials)
-      QP_CHECK(qp::launch_reduce_triples(ctx->stream, w->chk_part, qp::spmv_grid_size(A), w->chk_out + 3 * (m - 1), &ctx->stats));
-    if (m == 1) {
-      sc.c *= 2.0;  // :184
-      prev = P;
-      cur = B;
-    } else {
-      std::swap(cur, prev);      // prev's buffer now holds v_m: it is gathered next
-    }
+      QP_CHECK(qp::launch_reduce_triples(ctx->stream, w->chk_part, qp::spmv_grid_size(A), w->chk_out + 3 * (L.m - 1), &ctx->stats));
   }
-  if (result != P)
-    QP_HIP(hipMemcpyAsync(P, result, (size_t)psi->n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
+  if (seq.result() != ChebySlot::Psi)
+    QP_HIP(hipMemcpyAsync(psi->d, buf[(int)seq.result()], (size_t)psi->n * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
   return QP_OK;
 }
 
 // does the persistent small-system kernel take a Chebychev time grid of this operator, and with which plan?  (Also behind
-// qp_operator_small_plan.)
+// qp_operator_small_plan; the gate on plain numbers: cheby_plan.h.)
 bool cheby_small_fits(const qp_operator* op, qp::SmallPlan* plan) {
-  const qp_ctx* ctx = op->ctx;
-  if (!(ctx->tun.small_nnz > 0 && op->A.nnz <= 2 * (int64_t)ctx->tun.small_nnz && op->nops <= 64)) return false;
-  const int64_t n = op->A.nrows;
-  const int64_t maxrow = operator_longest_row(op);
-  // 16 register slots per lane where that is enough; otherwise 32 (the upper 16 values of a lane
-  // live in LDS: 128 KB, which leaves room for vectors of up to 600 rows)
-  bool ok = op->A.nnz <= ctx->tun.small_nnz && qp::small_plan(n, maxrow, plan, qp::kSmallEpt);
-  if (!ok && n <= 600) ok = qp::small_plan(n, maxrow, plan, 2 * qp::kSmallEpt);
-  return ok;
+  const int small_nnz = op->ctx->tun.small_nnz;
+  return cheby_small_candidate(op->A.nnz, op->nops, small_nnz) &&
+         cheby_small_gate(op->A.nnz, op->nops, op->A.nrows, operator_longest_row(op), small_nnz, plan);
+}
+
+// the argument checks every cheby! entry point shares, in the reference's words (`dt` nullable: no time step to compare)
+static int cheby_step_args(const double* dt, double wrk_dt, int n_coeffs, double Delta) {
+  if (dt && !cheby_dt_matches(*dt, wrk_dt)) return qp::fail(QP_E_DT_MISMATCH, "wrk was initialized for dt=%g, not dt=abs(%g)", wrk_dt, *dt);
+  if (n_coeffs < 2) return qp::fail(QP_E_TOO_FEW_COEFFS, "Need at least 2 Chebychev coefficients");
+  if (!(Delta > 0)) return qp::fail(QP_E_BAD_ARG, "Delta must be positive");
+  return QP_OK;
+}
+
+// Launch-bound systems (a term takes less than its launch): the step of `launch` as a hipGraph, replayed while the key --
+// everything a launch argument is derived from -- stays the same; the second identical call in a row records it.  *done = false:
+// nothing was issued (the caller launches the step itself).  Never for a matrix-free operator: the key knows an operator by its
+// stored arrays (all NULL there), and the owner's launch picks its kernel on the host from the CURRENT coefficients
+// (engine_pauli.hip: real-only paths, diagonal vector real or complex) -- a captured step would replay another operator's, or an
+// earlier coefficient set's, launches
+template <class Launch>
+static int cheby_step_graph(qp_cheby* w, qp_operator* op, qp_state* psi, const double* a, int n_coeffs, double Delta, double E_min,
+                            double dt, Launch&& launch, bool* done) {
+  qp_ctx* ctx = op->ctx;
+  const DevMatrix& A = op->A;
+  *done = false;
+  if (!ctx->tun.cheby_graph || A.format == QP_FMT_MATFREE || ctx->stream == nullptr || ctx->stream == hipStreamLegacy) return QP_OK;
+  qp_cheby::GraphKey key;
+  key.vals = A.vals_r ? (const void*)A.vals_r : (const void*)A.vals;
+  key.cols = A.cols;
+  key.rowptr = qp::csr_layout(A.format) ? (const void*)A.rowptr : (const void*)A.bptr;
+  key.psi = psi->d;
+  key.format = A.format;
+  // every knob that selects a kernel or a launch shape of the step's terms
+  key.variant = ((((ctx->tun.rbcsr_variant * 2) * 16 + 8) * 2 + (ctx->tun.hrb_walk ? 1 : 0)) * 8 +
+                 (ctx->tun.walk_nt & 7)) * 4096 + (ctx->tun.walk_waves & 4095);
+  key.variant = key.variant * 2 + (ctx->tun.value_dict ? 1 : 0);      // (coded / plain row-block kernel)
+  key.variant = key.variant * 2 + (walk2_wanted(op) ? 1 : 0);         // (terms in pairs)
+  key.n_coeffs = n_coeffs;
+  key.dt = dt;
+  key.Delta = Delta;
+  key.E_min = E_min;
+  uint64_t h = 1469598103934665603ull;   // FNV-1a over the coefficient bits
+  for (int i = 0; i < n_coeffs; ++i) {
+    uint64_t bits;
+    std::memcpy(&bits, &a[i], 8);
+    h = (h ^ bits) * 1099511628211ull;
+  }
+  key.a_hash = h;
+  if (!(w->gexec && key == w->gkey)) {
+    if (!(key == w->gpending && (int64_t)spmv_grid_size(A) <= ctx->tun.cheby_graph)) {
+      w->gpending = key;
+      return QP_OK;
+    }
+    // second identical call in a row: record it
+    hipGraph_t graph = nullptr;
+    const Stats before = ctx->stats;
+    QP_HIP(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+    const int rc = launch();
+    w->gstats = Stats();
+    w->gstats.n_matvec = ctx->stats.n_matvec - before.n_matvec;
+    w->gstats.n_launch = ctx->stats.n_launch - before.n_launch;
+    w->gstats.spmv_bytes = ctx->stats.spmv_bytes - before.spmv_bytes;
+    ctx->stats = before;
+    const hipError_t ec = hipStreamEndCapture(ctx->stream, &graph);
+    if (rc != QP_OK) {
+      if (graph) (void)hipGraphDestroy(graph);
+      return rc;
+    }
+    QP_HIP(ec);
+    if (w->gexec) {
+      (void)hipGraphExecDestroy(w->gexec);
+      w->gexec = nullptr;
+    }
+    const hipError_t ei = hipGraphInstantiate(&w->gexec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    QP_HIP(ei);
+    w->gkey = key;
+  }
+  QP_HIP(hipGraphLaunch(w->gexec, ctx->stream));
+  ctx->stats.n_graph_launch++;
+  ctx->stats.n_matvec += w->gstats.n_matvec;
+  ctx->stats.n_launch += w->gstats.n_launch;
+  ctx->stats.spmv_bytes += w->gstats.spmv_bytes;
+  *done = true;
+  return QP_OK;
 }
 
 extern "C" {
@@ -297,9 +298,7 @@ int qp_cheby_step(qp_cheby* w, qp_operator* op, qp_state* psi, const double* a, 
   if (!w || !op || !psi || !a) return qp::fail(QP_E_BAD_ARG, "qp_cheby_step: NULL argument");
   if (op->A.nrows != op->A.ncols || psi->n != op->A.nrows || w->n != psi->n)
     return qp::fail(QP_E_BAD_ARG, "qp_cheby_step: shape mismatch");
-  if (!cheby_dt_matches(dt, wrk_dt)) return qp::fail(QP_E_DT_MISMATCH, "wrk was initialized for dt=%g, not dt=abs(%g)", wrk_dt, dt);
-  if (n_coeffs < 2) return qp::fail(QP_E_TOO_FEW_COEFFS, "Need at least 2 Chebychev coefficients");
-  if (!(Delta > 0)) return qp::fail(QP_E_BAD_ARG, "Delta must be positive");
+  QP_CHECK(cheby_step_args(&dt, wrk_dt, n_coeffs, Delta));
   qp_ctx* ctx = op->ctx;
   QP_CHECK(use(ctx));
   const qp::ScopedRange step_range(ctx->tun.roctx != 0 || qp::ranges_enabled_by_env(), "prop_step!");   // src/cheby_propagator.jl:349
@@ -325,94 +324,22 @@ int qp_cheby_step(qp_cheby* w, qp_operator* op, qp_state* psi, const double* a, 
   }
   // the two-term strip walk rotates four term vectors: the two beyond Psi's and bufA are allocated on first use (here, not inside a
   // stream capture)
-  if (nterms >= 3 && !check_normalization && !w->bufC && walk2_wanted(op)) {
+  if (ChebySequence::pairs_possible(n_coeffs, check_normalization != 0, false) && !w->bufC && walk2_wanted(op)) {
     QP_CHECK(dev_alloc(&w->bufC, (size_t)w->n));
     QP_CHECK(dev_alloc(&w->bufD, (size_t)w->n));
   }
-  // launch-bound systems (a term takes less than its launch): replay the step as a hipGraph.  Never for a matrix-free operator:
-  // the key below knows an operator by its stored arrays (all NULL there), and the owner's launch picks its kernel on the host from
-  // the CURRENT coefficients (engine_pauli.hip: real-only paths, diagonal vector real or complex) -- a captured step would replay
-  // another operator's, or an earlier coefficient set's, launches
+  auto launches = [&] { return cheby_step_launches(w, op, psi, a, n_coeffs, sc, check_normalization != 0, false, launch_term); };
   bool done = false;
-  if (ctx->tun.cheby_graph && !check_normalization && A.format != QP_FMT_MATFREE && ctx->stream != nullptr &&
-      ctx->stream != hipStreamLegacy) {
-    qp_cheby::GraphKey key;
-    key.vals = A.vals_r ? (const void*)A.vals_r : (const void*)A.vals;
-    key.cols = A.cols;
-    key.rowptr = qp::csr_layout(A.format) ? (const void*)A.rowptr : (const void*)A.bptr;
-    key.psi = psi->d;
-    key.format = A.format;
-    // every knob that selects a kernel or a launch shape of the step's terms
-    key.variant = ((((ctx->tun.rbcsr_variant * 2) * 16 + 8) * 2 + (ctx->tun.hrb_walk ? 1 : 0)) * 8 +
-                   (ctx->tun.walk_nt & 7)) * 4096 + (ctx->tun.walk_waves & 4095);
-    key.variant = key.variant * 2 + (ctx->tun.value_dict ? 1 : 0);      // (coded / plain row-block kernel)
-    key.variant = key.variant * 2 + (walk2_wanted(op) ? 1 : 0);         // (terms in pairs)
-    key.n_coeffs = n_coeffs;
-    key.dt = dt;
-    key.Delta = Delta;
-    key.E_min = E_min;
-    uint64_t h = 1469598103934665603ull;   // FNV-1a over the coefficient bits
-    for (int i = 0; i < n_coeffs; ++i) {
-      uint64_t bits;
-      std::memcpy(&bits, &a[i], 8);
-      h = (h ^ bits) * 1099511628211ull;
-    }
-    key.a_hash = h;
-    auto replay = [&]() -> int {
-      QP_HIP(hipGraphLaunch(w->gexec, ctx->stream));
-      ctx->stats.n_graph_launch++;
-      ctx->stats.n_matvec += w->gstats.n_matvec;
-      ctx->stats.n_launch += w->gstats.n_launch;
-      ctx->stats.spmv_bytes += w->gstats.spmv_bytes;
-      return QP_OK;
-    };
-    if (w->gexec && key == w->gkey) {
-      QP_CHECK(replay());
-      done = true;
-    } else if (key == w->gpending && (int64_t)spmv_grid_size(A) <= ctx->tun.cheby_graph) {
-      // second identical call in a row: record it
-      hipGraph_t graph = nullptr;
-      const Stats before = ctx->stats;
-      QP_HIP(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-      const int rc = cheby_step_launches(w, op, psi, a, n_coeffs, sc, false, false, launch_term);
-      w->gstats = Stats();
-      w->gstats.n_matvec = ctx->stats.n_matvec - before.n_matvec;
-      w->gstats.n_launch = ctx->stats.n_launch - before.n_launch;
-      w->gstats.spmv_bytes = ctx->stats.spmv_bytes - before.spmv_bytes;
-      ctx->stats = before;
-      const hipError_t ec = hipStreamEndCapture(ctx->stream, &graph);
-      if (rc != QP_OK) {
-        if (graph) (void)hipGraphDestroy(graph);
-        return rc;
-      }
-      QP_HIP(ec);
-      if (w->gexec) {
-        (void)hipGraphExecDestroy(w->gexec);
-        w->gexec = nullptr;
-      }
-      const hipError_t ei = hipGraphInstantiate(&w->gexec, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      QP_HIP(ei);
-      w->gkey = key;
-      QP_CHECK(replay());
-      done = true;
-    } else {
-      w->gpending = key;
-    }
-  }
-  if (!done) QP_CHECK(cheby_step_launches(w, op, psi, a, n_coeffs, sc, check_normalization != 0, false, launch_term));
+  if (!check_normalization) QP_CHECK(cheby_step_graph(w, op, psi, a, n_coeffs, Delta, E_min, dt, launches, &done));
+  if (!done) QP_CHECK(launches());
   ctx->stats.n_cheby_steps++;
   if (check_normalization && nterms >= 2) {
     std::vector<double> h((size_t)3 * nterms);
     QP_HIP(hipMemcpyAsync(h.data(), w->chk_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     QP_HIP(hipStreamSynchronize(ctx->stream));
-    for (int m = 2; m <= nterms; ++m) {
-      const double* t = &h[3 * (m - 1)];
-      const double map_norm = std::hypot(t[0], t[1]) / (2 * t[2]);   // :195
-      if (!(map_norm <= 1.0 + limit)) {
-        w->bad_term = m + 1;   // (coefficient a[m + 1] of the reference's 1-based list)
-        return qp::fail(QP_E_NORMALIZATION, "Incorrect normalization (E_min=%g, Delta=%g) in term %d", E_min, Delta, m + 1);
-      }
+    if (const int bad = cheby_normalization_verdict(h.data(), nterms, limit)) {
+      w->bad_term = bad;
+      return qp::fail(QP_E_NORMALIZATION, "Incorrect normalization (E_min=%g, Delta=%g) in term %d", E_min, Delta, bad);
     }
   }
   return QP_OK;
@@ -430,9 +357,7 @@ int qp_cheby_step_batched(qp_cheby* w, qp_operator* op, qp_state* psi, int batch
   if (op->A.nrows != op->A.ncols || psi->n != n * batch || w->n != psi->n)
     return qp::fail(QP_E_BAD_ARG, "qp_cheby_step_batched: shape mismatch (operator %lld, batch %d, panel %lld)",
                     (long long)n, batch, (long long)psi->n);
-  if (!cheby_dt_matches(dt, wrk_dt)) return qp::fail(QP_E_DT_MISMATCH, "wrk was initialized for dt=%g, not dt=abs(%g)", wrk_dt, dt);
-  if (n_coeffs < 2) return qp::fail(QP_E_TOO_FEW_COEFFS, "Need at least 2 Chebychev coefficients");
-  if (!(Delta > 0)) return qp::fail(QP_E_BAD_ARG, "Delta must be positive");
+  QP_CHECK(cheby_step_args(&dt, wrk_dt, n_coeffs, Delta));
   qp_ctx* ctx = op->ctx;
   QP_CHECK(use(ctx));
   // a dense operator (QP_FMT_DENSE): H X on the fp64 matrix cores (csrc/kernels_dense.hip), straight from the operator's own
@@ -471,59 +396,22 @@ int qp_split_create(qp_operator* op, const int64_t* send_rows, int64_t nsend, qp
   if (A.format != QP_FMT_RBCSR && A.format != QP_FMT_HRB)
     return qp::fail(QP_E_BAD_ARG, "qp_split_create needs a row-block device format (got %d)", A.format);
   QP_CHECK(use(op->ctx));
-  const auto& ur = op->u_rowptr;
-  const auto& uc = op->u_col;
-  std::vector<char> is_boundary((size_t)A.nblocks, 0);
-  std::vector<int32_t> slot_of_row((size_t)A.nrows, -1);
-  for (int64_t i = 0; i < nsend; ++i) {
-    const int64_t r = send_rows[i];
-    if (r < 0 || r >= A.nrows) return qp::fail(QP_E_BAD_ARG, "send row %lld out of range", (long long)r);
-    if (slot_of_row[r] >= 0) return qp::fail(QP_E_BAD_ARG, "send row %lld listed twice", (long long)r);
-    slot_of_row[r] = (int32_t)i;
-    is_boundary[r / kRB] = 1;
-  }
-  for (int64_t r = 0; r < A.nrows; ++r)   // rows that read a ghost column must wait for the exchange
-    if (ur[r + 1] > ur[r] && uc[ur[r + 1] - 1] >= A.nrows) is_boundary[r / kRB] = 1;
-  // interior blocks that exchange data with boundary rows inside the local block (they gather
-  // from boundary rows, or boundary rows gather from them) are listed last: only they have to
-  // wait for the boundary launch of the previous term
-  std::vector<char> adjacent((size_t)A.nblocks, 0);
-  for (int64_t r = 0; r < A.nrows; ++r) {
-    const bool rb_ = is_boundary[r / kRB];
-    for (int64_t p = ur[r]; p < ur[r + 1]; ++p) {
-      const int64_t c = uc[p];
-      if (c >= A.nrows) continue;
-      const bool cb = is_boundary[c / kRB];
-      if (rb_ && !cb) adjacent[c / kRB] = 1;
-      if (!rb_ && cb) adjacent[r / kRB] = 1;
-    }
-  }
-  std::vector<int32_t> bb, bi, bi_adj;
-  for (int64_t b = 0; b < A.nblocks; ++b) {
-    if (is_boundary[b]) bb.push_back((int32_t)b);
-    else if (adjacent[b]) bi_adj.push_back((int32_t)b);
-    else bi.push_back((int32_t)b);
-  }
-  const unsigned wait_from_wg = (unsigned)(bi.size() / (qp::kThreads / 64));
-  bi.insert(bi.end(), bi_adj.begin(), bi_adj.end());
-  std::vector<int32_t> mirror(bb.size() * kRB + 1, -1);
-  for (size_t k = 0; k < bb.size(); ++k)
-    for (int l = 0; l < kRB; ++l) {
-      const int64_t r = (int64_t)bb[k] * kRB + l;
-      if (r < A.nrows) mirror[k * kRB + l] = slot_of_row[r];
-    }
+  // the partition itself is plain data (cheby_plan.h: plan_split); the interior as a strip walk where the operator has a plan
+  const qp::WalkPlan* P = (A.walk && A.walk->valid && A.format == QP_FMT_HRB) ? A.walk : nullptr;
+  const SplitWalk pw = P ? SplitWalk{1, P->K, P->fd, P->g, P->glong, P->W0, P->R1} : SplitWalk();
+  SplitPlan plan;
+  QP_CHECK(plan_split(A.nrows, op->u_rowptr.data(), op->u_col.data(), send_rows, nsend, qp::kThreads / 64, pw, &plan));
   auto sp = std::make_unique<qp_split>();
   sp->op = op;
   sp->device = op->ctx->device;
-  sp->n_boundary = (int64_t)bb.size();
-  sp->n_interior = (int64_t)bi.size();
+  sp->n_boundary = (int64_t)plan.boundary.size();
+  sp->n_interior = (int64_t)plan.interior.size();
   sp->nsend = nsend;
-  QP_CHECK(dev_alloc(&sp->bmap_boundary, bb.size()));
-  QP_CHECK(dev_alloc(&sp->bmap_interior, bi.size()));
-  QP_CHECK(dev_alloc(&sp->mirror, mirror.size()));
-  if (!bb.empty()) QP_HIP(hipMemcpy(sp->bmap_boundary, bb.data(), bb.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  if (!bi.empty()) QP_HIP(hipMemcpy(sp->bmap_interior, bi.data(), bi.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  QP_HIP(hipMemcpy(sp->mirror, mirror.data(), mirror.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  sp->wait_from_wg = plan.wait_from_wg;
+  sp->n_waiting_wg = plan.n_waiting_wg;
+  QP_CHECK(dev_upload(&sp->bmap_boundary, plan.boundary.data(), plan.boundary.size()));
+  QP_CHECK(dev_upload(&sp->bmap_interior, plan.interior.data(), plan.interior.size()));
+  QP_CHECK(dev_upload(&sp->mirror, plan.mirror.data(), plan.mirror.size()));
   QP_HIP(hipEventCreateWithFlags(&sp->ev_b, hipEventDisableTiming));
   QP_HIP(hipEventCreateWithFlags(&sp->ev_i, hipEventDisableTiming));
   QP_CHECK(dev_alloc(&sp->counter, 2));
@@ -531,37 +419,13 @@ int qp_split_create(qp_operator* op, const int64_t* send_rows, int64_t nsend, qp
   QP_HIP(hipHostMalloc((void**)&sp->timeout_host, sizeof(unsigned), hipHostMallocMapped));
   *sp->timeout_host = 0;
   QP_HIP(hipHostGetDevicePointer((void**)&sp->timeout_dev, sp->timeout_host, 0));
-  // Interior as a strip walk.  The boundary blocks of a row-partitioned lattice are a prefix and a suffix of the local
-  // rows; the walk takes the interior blocks from which no walked row block, with its ring of +-K strip steps and its
-  // one-block halo, reaches a boundary block: [max(W0, lo + K S + 1), min(R1, hi - K S - 1)).
-  sp->walk = qp::WalkPlan();
-  if (op->A.walk && op->A.walk->valid && op->A.format == QP_FMT_HRB) {
-    const qp::WalkPlan& P = *op->A.walk;
-    int64_t lo = 0, hi = A.nblocks;
-    while (lo < A.nblocks && is_boundary[lo]) ++lo;
-    while (hi > lo && is_boundary[hi - 1]) --hi;
-    bool contiguous = true;
-    for (int64_t b = lo; b < hi && contiguous; ++b) contiguous = !is_boundary[b];
-    const int64_t reach = (std::max<int64_t>((int64_t)P.K * P.g + P.fd, P.glong) + kRB - 1) / kRB + 1;
-    const int64_t w0 = std::max(P.W0, lo + reach), r1 = std::min(P.R1, hi - reach);
-    if (contiguous && r1 - w0 >= 8) {
-      std::vector<int32_t> edge;
-      for (int32_t b : bi)
-        if (b < w0 || b >= r1) edge.push_back(b);
-      qp::WalkPlan W = P;
-      W.W0 = w0;
-      W.R1 = r1;
-      W.edge_map = nullptr;
-      W.n_edge = (int64_t)edge.size();
-      QP_CHECK(dev_alloc(&W.edge_map, std::max<size_t>(edge.size(), 1)));
-      if (!edge.empty()) QP_HIP(hipMemcpy(W.edge_map, edge.data(), edge.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-      sp->walk = W;
-    }
-  }
-  sp->wait_from_wg = wait_from_wg;
-  {
-    const unsigned total = (unsigned)((bi.size() + qp::kThreads / 64 - 1) / (qp::kThreads / 64));
-    sp->n_waiting_wg = total > wait_from_wg ? total - wait_from_wg : 0;
+  if (plan.walk) {
+    qp::WalkPlan W = *A.walk;
+    W.W0 = plan.W0;
+    W.R1 = plan.R1;
+    W.n_edge = (int64_t)plan.edge.size();
+    QP_CHECK(dev_upload(&W.edge_map, plan.edge.data(), plan.edge.size()));
+    sp->walk = W;
   }
   *out = sp.release();
   return QP_OK;
@@ -696,11 +560,9 @@ static int propagate_cheby_small(qp_operator* op, qp_state* psi, const qp_prop_s
   const size_t rows = (size_t)nsteps + 1;
   if (!w || !spec->a) return qp::fail(QP_E_BAD_ARG, "qp_propagate: NULL Chebychev workspace");
   if (op->A.nrows != op->A.ncols || n != op->A.nrows || w->n != n) return qp::fail(QP_E_BAD_ARG, "qp_propagate: shape mismatch");
-  if (spec->n_coeffs < 2) return qp::fail(QP_E_TOO_FEW_COEFFS, "Need at least 2 Chebychev coefficients");
-  if (!(spec->Delta > 0)) return qp::fail(QP_E_BAD_ARG, "Delta must be positive");
+  QP_CHECK(cheby_step_args(nullptr, spec->wrk_dt, spec->n_coeffs, spec->Delta));
   for (int k = 0; k < nsteps; ++k) {
-    if (!cheby_dt_matches(dts[k], spec->wrk_dt))
-      return qp::fail(QP_E_DT_MISMATCH, "wrk was initialized for dt=%g, not dt=abs(%g)", spec->wrk_dt, dts[k]);
+    QP_CHECK(cheby_step_args(&dts[k], spec->wrk_dt, spec->n_coeffs, spec->Delta));
     if ((dts[k] > 0) != (dts[0] > 0)) return qp::fail(QP_E_BAD_ARG, "qp_propagate: time steps change sign");
   }
   QP_CHECK(operator_csr_mirror(op));

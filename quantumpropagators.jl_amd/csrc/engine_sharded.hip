@@ -287,9 +287,7 @@ int qp_sharded_cheby_step(qp_sharded_cheby* s, const double* a, int n_coeffs, do
   qp_ctx* ctx = s->ctx;
   QP_CHECK(use(ctx));
   const int64_t nloc = s->nloc;
-  const int nterms = n_coeffs - 1;
-  ChebyScalars sc(Delta, E_min, dt);
-  ChebyAcc acc(a, n_coeffs, ctx->tun.acc_defer != 0);
+  const ChebyScalars sc(Delta, E_min, dt);
   const bool exchanging = d.M > 0;
   const bool overlap = d.split != nullptr;
   hipStream_t S_c = ctx->stream;
@@ -355,34 +353,33 @@ int qp_sharded_cheby_step(qp_sharded_cheby* s, const double* a, int n_coeffs, do
     QP_HIP(hipStreamWaitEvent(S_x, s->ev_main, 0));
   }
   QP_CHECK(exchange(0, false));
-  bool result_in_acc = true;
-  for (int m = 1; m <= nterms; ++m) {
-    const bool last = (m == nterms);
-    const int xi = (m % 2 == 1) ? 0 : 1, oi = 1 - xi;
-    const ChebyAcc::Term t = acc.term(m);
-    const qp_acc_defer& df = *t.defer;
-    const qp_c128 cc{sc.c.real(), sc.c.imag()};
+  // the terms of the step and their vectors: ChebySequence (cheby_plan.h) with Psi = X0, A = X1, never in pairs -- the state
+  // buffer X0 is an output only while it is not being gathered
+  qp_state* const loc[kChebySlots] = {nullptr, &xloc[0], &xloc[1], nullptr, nullptr, d.acc};   // (ChebySlot)
+  ChebySequence seq(a, n_coeffs, ctx->tun.acc_defer != 0, false, false, false);
+  ChebyLaunch L;
+  while (seq.next(&L)) {
+    const ChebyTerm& t = L.t[0];
+    const bool last = t.apply_phase != 0;
+    const int xi = (t.x == ChebySlot::Psi) ? 0 : 1, oi = 1 - xi;
+    const qp::cplx c = sc.c * t.c_scale;
+    const qp_c128 cc{c.real(), c.imag()};
     const qp_c128 ph = last ? qp_c128{sc.phase.real(), sc.phase.imag()} : qp_c128{1.0, 0.0};
-    const qp_state* v0 = (m == 1) ? nullptr : &xloc[oi];
-    qp_state* vout = last ? nullptr : &xloc[oi];
-    const qp_state* acc_in = t.acc_in ? d.acc : nullptr;
-    // the state buffer X0 may be written only while it is not being gathered
-    qp_state* out = (m > 1 && last && xi == 1) ? &xloc[0] : d.acc;
-    if (!df.skip && m > 1) result_in_acc = (out == d.acc);
     if (overlap) {
-      QP_CHECK(qp_cheby_term_split(d.op, d.split, (void*)S_x, m == 1 ? 1 : 0, X[xi], 0, v0, vout, acc_in,
-                                   df.skip ? nullptr : out, last ? nullptr : d.slab, cc, sc.beta, t.a_prev, a[m], ph, &df));
+      QP_CHECK(qp_cheby_term_split(d.op, d.split, (void*)S_x, t.m == 1 ? 1 : 0, X[xi], 0, loc[(int)t.v0], loc[(int)t.vout],
+                                   loc[(int)t.acc_in], loc[(int)t.acc_out], last ? nullptr : d.slab, cc, sc.beta, t.a_prev, t.a, ph,
+                                   t.defer));
     } else {
-      QP_CHECK(qp_cheby_term(d.op, X[xi], 0, v0, vout, acc_in, df.skip ? nullptr : out, cc, sc.beta, t.a_prev, a[m], ph, &df));
+      QP_CHECK(qp_cheby_term(d.op, X[xi], 0, loc[(int)t.v0], loc[(int)t.vout], loc[(int)t.acc_in], loc[(int)t.acc_out], cc, sc.beta,
+                             t.a_prev, t.a, ph, t.defer));
     }
     if (!last) QP_CHECK(exchange(oi, overlap));
-    if (m == 1) sc.c *= 2.0;                                               // :184
   }
   if (overlap) {   // join back: later work on the main stream sees everything the side stream did
     QP_HIP(hipEventRecord(s->ev_side, S_x));
     QP_HIP(hipStreamWaitEvent(S_c, s->ev_side, 0));
   }
-  if (result_in_acc)
+  if (seq.result() != ChebySlot::Psi)
     QP_HIP(hipMemcpyAsync(d.X0->d, d.acc->d, (size_t)nloc * sizeof(double2), hipMemcpyDeviceToDevice, S_c));
   ctx->stats.n_cheby_steps++;
   if (overlap) QP_CHECK(split_timed_out(d.split));

@@ -1,5 +1,5 @@
 // Which instance of the persistent single-workgroup kernels (kernels_small.hip) a small system takes: lanes per row, entries per
-// lane and rows per lane group, as a pure function of plain numbers.  No HIP: the two gates (engine_cheby.hip: cheby_small_fits,
+// lane and rows per lane group, as a pure function of plain numbers.  No HIP: the two gates (cheby_plan.cpp: cheby_small_gate, behind engine_cheby.hip: cheby_small_fits;
 // engine_krylov.hip: small_sweep_fits), qp_small_plan_host and the tests of the non-GPU suite all call the same function.
 #pragma once
 

@@ -1,5 +1,5 @@
 """The persistent single-workgroup kernels (csrc/kernels_small.hip) as the tests see them: a Python mirror of the plan
-(csrc/small_plan.cpp) and of the two gates (csrc/engine_cheby.hip: cheby_small_fits, csrc/engine_krylov.hip: small_sweep_fits), the
+(csrc/small_plan.cpp) and of the two gates (csrc/cheby_plan.cpp: cheby_small_gate, csrc/engine_krylov.hip: small_sweep_fits), the
 instances `(ent, rows_per_group)` that an operator of at most 2048 rows can reach under the default knobs, and ONE table of the
 smallest operators that select each of them -- shared by tests/test_small_plan_host.py (no GPU: mirror against the library, the
 table against the reachable set) and tests/test_gpu_small_instances.py (every case on the device).  NumPy / SciPy only."""
@@ -14,7 +14,7 @@ SLOTS_WIDE = 32        # kSmallEptArnoldi, and the packed Chebychev form
 LDS_ROWS = 2048        # kSmallLdsRows
 LDS_BYTES = 152 * 1024  # kSmallLdsBytes
 SMALL_NNZ = 8192       # csrc/device.h: Tuning::small_nnz
-CHEBY_WIDE_ROWS = 600  # engine_cheby.hip: the 32-slot Chebychev form keeps 128 KB of values in LDS, which leaves room for 600 rows
+CHEBY_WIDE_ROWS = 600  # cheby_plan.cpp (cheby_small_gate): the 32-slot Chebychev form keeps 128 KB of values in LDS, which leaves room for 600 rows
 
 
 def small_plan(n, maxrow, max_slots=SLOTS):
@@ -38,7 +38,7 @@ def small_plan(n, maxrow, max_slots=SLOTS):
 
 
 def cheby_plan(n, nnz, maxrow, nops=1, small_nnz=SMALL_NNZ):
-    """What qp_propagate (method 0) takes -- csrc/engine_cheby.hip: cheby_small_fits."""
+    """What qp_propagate (method 0) takes -- csrc/cheby_plan.cpp: cheby_small_gate."""
     if not (small_nnz > 0 and nnz <= 2 * small_nnz and nops <= 64):
         return None
     plan = small_plan(n, maxrow, SLOTS) if nnz <= small_nnz else None

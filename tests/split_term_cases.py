@@ -2,7 +2,7 @@
 tests/test_gpu_split_term.py runs them through qp_split_create / qp_cheby_term_split, tests/test_split_term_cases_host.py (no GPU)
 shows with a host emulation that the same helpers reject a wrong slot, a block taken twice or not at all and a store past the slab.
 
-partition(A, send_rows) restates, from the SciPy matrix alone, what qp_split_create (csrc/engine_cheby.hip) must decide about the
+partition(A, send_rows) restates, from the SciPy matrix alone, what qp_split_create (its partition: csrc/cheby_plan.cpp, plan_split) must decide about the
 64-row blocks of a rank's local rows (nrows x ncols, a column >= nrows being a ghost column: an entry of another rank's rows):
 
     boundary   a block with a send row, or with a row whose largest column is a ghost column

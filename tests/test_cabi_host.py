@@ -508,6 +508,48 @@ def test_host_index_work_under_sanitizers(tmp_path):
         _require_every_site_threaded(csrc, large.stdout)
 
 
+def test_cheby_plan_host_under_sanitizers(tmp_path):
+    """The pure-host planning unit of cheby! (csrc/cheby_plan.cpp: the launches of a step with the vector every term gathers, reads
+    and writes, the boundary / interior partition of a split term, the small-system gate, the verdict of check_normalization) needs
+    no HIP stand-in to compile, and tests/cheby_plan_host.cpp -- built from it and csrc/small_plan.cpp alone with
+    g++ -fsanitize=address,undefined -- holds it by construction (every sequence of 2 .. 40 coefficients replayed symbolically,
+    pairs off / accepted / refused; every partition against brute-force definitions) and against the rows the commit before the
+    unit printed (tests/cheby_plan_cases.h).  Nothing is loaded into Python."""
+    import re
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    csrc = os.path.join(ROOT, "quantumpropagators.jl_amd", "csrc")
+    pure = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", csrc, os.path.join(csrc, "cheby_plan.cpp")], capture_output=True, text=True)
+    assert pure.returncode == 0, pure.stderr[-3000:]
+    exe = str(tmp_path / "cheby_plan_san")
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            "-I", csrc, "-I", os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "cheby_plan_host.cpp"),
+                            os.path.join(csrc, "cheby_plan.cpp"), os.path.join(csrc, "small_plan.cpp"), "-o", exe],
+                           capture_output=True, text=True)
+    if build.returncode != 0 and "sanitize" in build.stderr and "cannot find" in build.stderr:
+        pytest.skip("sanitizer runtime not installed")
+    assert build.returncode == 0, build.stderr[-3000:]
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
+    assert "sanitizer run clean" in run.stdout
+    n = re.search(r"rotation: (\d+) sequences of 2 \.\. 40 coefficients replayed", run.stdout)
+    assert n and int(n.group(1)) >= 39 * 2 * 2 * 2, run.stdout
+    named = re.search(r"rotation: (\d+) named sequences \((\d+) launch rows\) match the table", run.stdout)
+    assert named and int(named.group(1)) >= 8 * 2 * 3 + 2 and int(named.group(2)) >= 300, run.stdout
+    split = re.search(r"split: (\d+) partitions match their definitions, (\d+) of them with a walk window; 3 refusals", run.stdout)
+    assert split and int(split.group(1)) >= 7 * 2 * 2 * 6 + 2 * 6 and int(split.group(2)) >= 8, run.stdout
+    assert re.search(r"split: 1[2-9] named partitions match the table", run.stdout), run.stdout
+    assert re.search(r"small gate: \d+ argument sets match the statement", run.stdout), run.stdout
+    # the table's rows come out of the current tree as they stand in the header
+    printed = subprocess.run([exe, "--print-cases"], capture_output=True, text=True, timeout=300)
+    assert printed.returncode == 0
+    with open(os.path.join(ROOT, "tests", "cheby_plan_cases.h")) as f:
+        header = f.read()
+    assert header.endswith(printed.stdout) and printed.stdout.count("\n") > 400
+
+
 def _cpus():
     """CPUs the box offers the library's host threads (csrc/operator_layout.h: host_threads reads the same two sources)"""
     n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)

@@ -38,7 +38,7 @@ def _ragged(n=200, seed=3):
 
 @pytest.mark.parametrize("n_coeffs", range(2, 13))
 def test_schedule_replayed_through_the_term_reference_is_the_oracle_step(n_coeffs):
-    """The terms of cheby_step_launches (csrc/engine_cheby.hip) with the schedule of qp_acc_schedule_host, each evaluated by
+    """The terms of a step without pairs (csrc/cheby_plan.cpp: ChebySequence, launched by cheby_step_launches of csrc/engine_cheby.hip) with the schedule of qp_acc_schedule_host, each evaluated by
     term_ref: v_1 = c (H v_0 - beta v_0), c doubled after the first term, v_m = c (H v_{m-1} - beta v_{m-1}) + v_{m-2}; the
     accumulator starts as a_0 v_0 inside the first update and takes the skipped terms' coefficients as a_d1 / a_d2; the phase on the
     last term.  Against oracle.qp_oracle.cheby (src/cheby.jl:171-211) to a few ulps of the unit state norm: 64 ulp = 1.4e-14 (the
