@@ -123,6 +123,9 @@ typedef struct {
   uint64_t n_kernel_launches;
   double spmv_bytes;       /* algorithmic bytes of fused mat-vec kernels */
   uint64_t n_graph_launches; /* hipGraph replays of a whole cheby! step (their kernels are counted above) */
+  uint64_t n_pair_launches;  /* two-term strip walk launches issued (two mat-vecs and two kernel launches each, counted above:
+                                n_matvec and n_kernel_launches are the same with and without pairs; a pair the launcher refused
+                                is not counted) */
 } qp_stats;
 int qp_stats_get(qp_ctx* ctx, qp_stats* out);
 int qp_stats_reset(qp_ctx* ctx);

@@ -186,6 +186,7 @@ struct PlainEpi {
 
 struct Stats {
   uint64_t n_matvec = 0, n_cheby_steps = 0, n_newton_steps = 0, n_restarts = 0, n_launch = 0, n_graph_launch = 0;
+  uint64_t n_pair_launch = 0;   // two-term strip walk launches that were issued (a refused pair is not one)
   double spmv_bytes = 0;
 };
 

@@ -98,6 +98,7 @@ static int cheby_step_launches(qp_cheby* w, qp_operator* op, qp_state* psi, cons
       rs.count = false;
       QP_CHECK(qp::launch_spmv_cheby(ctx->stream, A, e2.xloc, e2, &ctx->stats, &rs));
       ctx->stats.n_launch++;
+      ctx->stats.n_pair_launch++;
       ctx->stats.n_matvec += 2;
       ctx->stats.spmv_bytes += 2.0 * (20.0 * (double)A.nnz + 4.0 * (double)(A.nrows + 1) + 80.0 * (double)A.nrows);
       continue;

@@ -253,6 +253,7 @@ int qp_stats_get(qp_ctx* ctx, qp_stats* out) {
   out->n_kernel_launches = ctx->stats.n_launch;
   out->spmv_bytes = ctx->stats.spmv_bytes;
   out->n_graph_launches = ctx->stats.n_graph_launch;
+  out->n_pair_launches = ctx->stats.n_pair_launch;
   return QP_OK;
 }
 

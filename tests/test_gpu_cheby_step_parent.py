@@ -189,7 +189,7 @@ def test_step_matches_parent(ctx, parent, name):
 
 
 def test_fixture_reaches_what_it_is_named_for(parent):
-    """the fixture itself: an odd and an even number of terms, the same bits with terms in pairs / without the deferred accumulator /
+    """the fixture itself: 35 and 22 coefficients (34 and 21 terms: an even and an odd number), the same bits with terms in pairs / without the deferred accumulator /
     with the check's extra launches / replayed, the gate separates the two grids, the splits walk or not"""
     assert set(parent) == set(STEP_CASES)
     for dt, n_coeffs in ((1.0, 35), (0.35, 22)):

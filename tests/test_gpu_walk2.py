@@ -65,7 +65,7 @@ def test_two_term_walk_bit_identical_to_one_term_launches(ctx, N, offsets, diag,
         assert wi["valid"] == 1 and (wi["near"], wi["far"], wi["diag"]) == shape
         psi0 = synth.random_state(N)
         results = {}
-        for dt in (1.0, 0.35):                 # 26 / 14 coefficients at Delta = 24: an odd and an even number of terms
+        for dt in (1.0, 0.35):                 # 35 / 22 coefficients at Delta = 24: 34 and 21 terms, an even and an odd number
             wrk = L.ChebyWrk(ctx, N, 24.0, -12.0, dt)
 
             def run(**knobs):
