@@ -223,9 +223,9 @@ int qp_operator_fill_info(const qp_operator* op, int64_t* n_filled);
  * (any g >= 64), out[5], out[6] = the walkable row blocks [W0, R1), out[7] = row blocks on the per-block path. */
 int qp_operator_walk_info(const qp_operator* op, int64_t out[8]);
 /* The two-term strip walk: whether a whole-operator qp_cheby_step of this operator forms TWO Chebyshev terms per pass over the
- * matrix values under the context's knobs (lattice operators beyond the Infinity Cache whose strip columns are long enough; knob
+ * matrix values under the context's knobs (lattice operators beyond the Infinity Cache whose strip columns are long enough, and complex ones inside it from 16 steps per wavefront; knob
  * walk_pair).  out[0] = 1 if it does, out[1], out[2] = the row blocks [W0, R1) that take both terms in one launch, out[3] = row
- * blocks outside them (two per-block launches per pair of terms), out[4] = rows of a 64-row column chunk that form the second
+ * blocks outside them (their first term inside the pair's launch, their second in a launch of its own), out[4] = rows of a 64-row column chunk that form the second
  * term (64 - 2 x the largest near distance: the chunks overlap), out[5] = chunks per strip step, out[6] = steps of the second term per
  * wavefront (each wavefront runs in 2 K steps before its first), out[7] = wavefronts per strip column.  Same results bit for bit
  * either way. */

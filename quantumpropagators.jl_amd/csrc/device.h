@@ -206,8 +206,11 @@ int launch_arnoldi_onepass_sweep(hipStream_t s, const DevMatrix& A, const double
                                  unsigned* flags_map, unsigned flag_value, Stats* st);
 // the strip walk for the fused Chebyshev term of a whole Hermitian-packed lattice operator; *launched = false when the
 // plan's shape has no kernel instance (the caller then takes the per-block kernel); how a launch is cut: walk_geometry.h
+// (two-term walk, kernels_walk2.hip: `rule` names the cut -- walk_geometry.h: walk2_rule; then term m + 1 of the plan's edge blocks,
+// one block per wavefront in three rounds of loads)
 int launch_hrb_walk2_cheby(hipStream_t s, const DevMatrix& A, const WalkPlan& P2, const double2* x, const ChebyEpi& e1,
-                           const ChebyEpi& e2, const Tuning& tun, bool* launched);
+                           const ChebyEpi& e2, const Tuning& tun, Walk2Rule rule, bool* launched);
+int launch_hrb_walk2_edge_cheby(hipStream_t s, const DevMatrix& A, const WalkPlan& P2, const double2* x, const ChebyEpi& e2);
 int launch_hrb_walk_cheby(hipStream_t s, const DevMatrix& A, const double2* x, const ChebyEpi& e, const Tuning& tun,
                           bool* launched, const RowSet* rs = nullptr);
 // kernels_dense.hip (QP_FMT_DENSE: CSR arrays with a complete pattern, i.e. vals / vals_r is the row-major dense matrix)
@@ -269,10 +272,10 @@ struct Tuning {
   int spmm_strip = 0;         // batched SpMM row walk: inner-index strip width (0 = chosen from the L2 size; -1 = natural row order)
   int hrb_walk = 1;           // Hermitian-packed fused term of a whole lattice operator: the strip-walk kernel (kernels_walk.hip) when the operator has a walk plan
   int walk_waves = 0;         // strip walk: wavefronts the walk is cut into (0: 768 for an operator that fits the Infinity Cache, else 8 per CU on every CU the edge workgroups leave free -- 1856 for the headline lattice --, or 2048 with the edge blocks inside the walk; the two-term walk: one per SIMD = 4 per compute unit)
-  int walk_pair = -1;         // strip walk, two Chebyshev terms per pass over the values (kernels_walk2.hip): -1 = for operators beyond the Infinity Cache whose strip columns are long enough (>= 24 steps per wavefront), 0 never, 1 wherever a plan exists (its cut: walk_waves)
+  int walk_pair = -1;         // strip walk, two Chebyshev terms per pass over the values (kernels_walk2.hip): -1 = for operators beyond the Infinity Cache whose strip columns are long enough (>= 24 steps per wavefront) and, with the resident cut, for operators with complex values inside it from 16 steps per wavefront (the headline at N = 2^20), 0 never, 1 wherever a plan exists (its cut: walk_waves), 2 wherever a plan exists, with the cut of cache-resident operators (walk_geometry.h: walk2_cut_resident)
   int value_dict = 1;         // value-dictionary mirror of row-block operators with few distinct values per block (0: never built / used)
   int walk_nt = -1;           // strip walk: nontemporal accesses (-1: the matrix values when the operator does not fit the Infinity Cache; bit 0 matrix values; bits 1, 2: vector loads, stores -- measurement variants of the headline shape)
-  int walk_dbg = 0;           // strip walk, measurements only: 1 = in-wave edge block after the walk instead of before it, 2 = edge blocks skipped (WRONG results), 4 = never as workgroups of their own
+  int walk_dbg = 0;           // strip walk, measurements only: 1 = in-wave edge block after the walk instead of before it, 2 = edge blocks skipped (WRONG results), 4 = never as workgroups of their own, 8 = a term pair's follow-up over the edge blocks by the per-block kernel, 16 | 32 | 64 = n: the resident pair cut with edge_steps = n - 1
   int walk_min_blocks = 3072; // strip walk: smallest number of walkable row blocks for which the plan is used
   int spmm_nt = 1;            // nontemporal matrix / row-local streams in the batched SpMM kernel: 0 never, 2 always, 1 for large panels
 };

@@ -200,11 +200,12 @@ struct qp_cheby {
   struct GraphKey {
     const void *vals = nullptr, *cols = nullptr, *rowptr = nullptr, *psi = nullptr;
     int format = -1, variant = -1, n_coeffs = 0;
+    int pair = 0;              // terms in pairs: the rule that fired (its cut) and the walk_dbg bits the pair launches read
     double dt = 0, Delta = 0, E_min = 0;
     uint64_t a_hash = 0;
     bool operator==(const GraphKey& o) const {
       return vals == o.vals && cols == o.cols && rowptr == o.rowptr && psi == o.psi && format == o.format &&
-             variant == o.variant && n_coeffs == o.n_coeffs && dt == o.dt && Delta == o.Delta && E_min == o.E_min &&
+             variant == o.variant && pair == o.pair && n_coeffs == o.n_coeffs && dt == o.dt && Delta == o.Delta && E_min == o.E_min &&
              a_hash == o.a_hash;
     }
   };

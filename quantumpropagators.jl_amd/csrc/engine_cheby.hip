@@ -56,11 +56,13 @@ static int cheby_term_args(const char* who, const qp_operator* op, const qp_stat
 
 // Does a whole-operator cheby! of `op` take the two-term strip walk (kernels_walk2.hip) under the context's knobs?  The rule:
 // walk_geometry.cpp, for an operator whose whole-operator term is the one-term walk of its own plan.
-static bool walk2_wanted(const qp_operator* op) {
+// Which of the two rules fired names the cut of the pair launches (walk_geometry.h: Walk2Rule).
+static qp::Walk2Rule walk2_rule(const qp_operator* op) {
   const qp::Tuning& tun = op->ctx->tun;
-  return tun.hrb_walk && (tun.rbcsr_variant & 31) == 15 && op->A.walk == &op->walk &&
-         qp::walk2_wanted(op->walk, op->walk2, qp::walk_matrix(op->A), qp::walk_knobs(tun), qp::device_cu_count());
+  if (!(tun.hrb_walk && (tun.rbcsr_variant & 31) == 15 && op->A.walk == &op->walk)) return qp::kWalk2None;
+  return qp::walk2_rule(op->walk, op->walk2, qp::walk_matrix(op->A), qp::walk_knobs(tun), qp::device_cu_count());
 }
+static bool walk2_wanted(const qp_operator* op) { return walk2_rule(op) != qp::kWalk2None; }
 
 // the launches of one cheby! call (src/cheby.jl:171-211): n_coeffs - 1 fused mat-vec + term kernels in the order and with the
 // vectors ChebySequence (cheby_plan.h) names, and, when the result does not land in Psi's buffer, one copy.
@@ -77,7 +79,8 @@ static int cheby_step_launches(qp_cheby* w, qp_operator* op, qp_state* psi, cons
                      sc.beta, t.a_prev, t.a, d2(sc.phase), t.apply_phase, t.defer);
   };
   // (qp_cheby_step allocated the two vectors of a step in pairs)
-  const bool pairs = ChebySequence::pairs_possible(n_coeffs, check_normalization, panel) && w->bufC && w->bufD && walk2_wanted(op);
+  const qp::Walk2Rule pair_rule = walk2_rule(op);
+  const bool pairs = ChebySequence::pairs_possible(n_coeffs, check_normalization, panel) && w->bufC && w->bufD && pair_rule != qp::kWalk2None;
   ChebySequence seq(a, n_coeffs, ctx->tun.acc_defer != 0, pairs, check_normalization, panel);
   ChebyLaunch L;
   while (seq.next(&L)) {
@@ -86,17 +89,22 @@ static int cheby_step_launches(qp_cheby* w, qp_operator* op, qp_state* psi, cons
       const qp::ChebyEpi e1 = epi(L.t[0]), e2 = epi(L.t[1]);
       bool launched = false;
       const qp::ScopedRange mv_range(ctx->tun.roctx != 0 || qp::ranges_enabled_by_env(), "matrix-vector product");
-      QP_CHECK(qp::launch_hrb_walk2_cheby(ctx->stream, A, op->walk2, e1.xloc, e1, e2, ctx->tun, &launched));
+      QP_CHECK(qp::launch_hrb_walk2_cheby(ctx->stream, A, op->walk2, e1.xloc, e1, e2, ctx->tun, pair_rule, &launched));
       if (!launched) {   // not taken after all (the kernel's LDS opt-in was refused): this and every later term as one-term launches
         seq.refuse();
         continue;
       }
       // term m + 1 of the blocks outside the two-term region: they read y of their neighbours, which the launch above wrote
-      qp::RowSet rs;
-      rs.block_map = op->walk2.edge_map;
-      rs.nmap = op->walk2.n_edge;
-      rs.count = false;
-      QP_CHECK(qp::launch_spmv_cheby(ctx->stream, A, e2.xloc, e2, &ctx->stats, &rs));
+      if (ctx->tun.walk_dbg & qp::kWalkDbgPairFollowUpPerBlock) {      // (A/B: the per-block kernel over the edge list as a row set)
+        qp::RowSet rs;
+        rs.block_map = op->walk2.edge_map;
+        rs.nmap = op->walk2.n_edge;
+        rs.count = false;
+        QP_CHECK(qp::launch_spmv_cheby(ctx->stream, A, e2.xloc, e2, &ctx->stats, &rs));
+      } else {
+        QP_CHECK(qp::launch_hrb_walk2_edge_cheby(ctx->stream, A, op->walk2, e2.xloc, e2));
+        ctx->stats.n_launch++;
+      }
       ctx->stats.n_launch++;
       ctx->stats.n_pair_launch++;
       ctx->stats.n_matvec += 2;
@@ -154,6 +162,7 @@ static int cheby_step_graph(qp_cheby* w, qp_operator* op, qp_state* psi, const d
                  (ctx->tun.walk_nt & 7)) * 4096 + (ctx->tun.walk_waves & 4095);
   key.variant = key.variant * 2 + (ctx->tun.value_dict ? 1 : 0);      // (coded / plain row-block kernel)
   key.variant = key.variant * 2 + (walk2_wanted(op) ? 1 : 0);         // (terms in pairs)
+  key.pair = (int)walk2_rule(op) * 128 + (ctx->tun.walk_dbg & 127);   // (... with which cut, follow-up kernel and edge steps)
   key.n_coeffs = n_coeffs;
   key.dt = dt;
   key.Delta = Delta;
@@ -264,10 +273,11 @@ int qp_cheby_term(qp_operator* op, const qp_state* x, int64_t xoff, const qp_sta
 int qp_operator_walk2_info(const qp_operator* op, int64_t out[8]) {
   QP_TRY
   if (!op || !out) return qp::fail(QP_E_BAD_ARG, "qp_operator_walk2_info: NULL argument");
-  const bool on = walk2_wanted(op);
+  const qp::Walk2Rule rule = walk2_rule(op);
+  const bool on = rule != qp::kWalk2None;
   // the cut the launcher gets (kernels_walk2.hip: launch_hrb_walk2_cheby): rows of a chunk that form z, chunks per strip step,
   // z steps per wavefront, segments per strip column
-  const qp::Walk2Cut C = on ? qp::walk2_cut(op->walk2, qp::walk_matrix(op->A), qp::walk_knobs(op->ctx->tun), qp::device_cu_count()) : qp::Walk2Cut();
+  const qp::Walk2Cut C = qp::walk2_cut_of(rule, op->walk2, qp::walk_matrix(op->A), qp::walk_knobs(op->ctx->tun), qp::device_cu_count());
   out[0] = on ? 1 : 0;
   out[1] = on ? op->walk2.W0 : 0;
   out[2] = on ? op->walk2.R1 : 0;

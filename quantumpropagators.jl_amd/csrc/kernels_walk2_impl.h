@@ -25,7 +25,8 @@
 //
 // Blocks outside the region where BOTH phases have their operands inside the lattice run -- the one-term walk's edge blocks and K strip
 // steps at either end of the run: the plan's edge list -- get term m from the per-block path inside this launch (before the walk,
-// they only read x and p) and term m + 1 from a per-block launch over the same list afterwards (engine_cheby.hip).
+// they only read x and p; the cut of cache-resident operators gives those wavefronts shorter segments, Walk2Geom::edge_steps) and
+// term m + 1 from a launch over the same list afterwards (kernels_walk2.hip: hrb_walk2_edge_kernel; engine_cheby.hip).
 //
 // Both row sums are the one-term walk's (lower slots then upper slots in storage order, two interleaved partial sums) and both
 // epilogues are ChebyOp's: bit-identical to one-term launches (tests/test_gpu_walk2.py).
@@ -67,15 +68,18 @@ __global__ __launch_bounds__(64 * kWalk2Waves) void hrb_walk2_kernel(const VT* _
   const int lane = threadIdx.x & 63;
   const unsigned wg = xcd_remap(blockIdx.x, G.n_walk_wg);
   const int task = (int)wg * kWalk2Waves + wave;
-  // term m of the blocks outside the two-term region: per-block path, before the walk
+  // term m of the blocks outside the two-term region: per-block path, before the walk (the block from the plan's bounds: one
+  // dependent load less than through edge_map)
   for (int64_t idx = task; idx < P.n_edge; idx += G.ntask)
-    hrb_edge_block<VT>(H, uvals, x, (int64_t)__builtin_amdgcn_readfirstlane(P.edge_map[idx]), lane, nrows, op1);
+    hrb_edge_block<VT>(H, uvals, x, walk_edge_block(P.W0, P.R1, idx), lane, nrows, op1);
   const int seg = task / G.S2, col = task - seg * G.S2;
   if (seg >= G.nseg) return;
   const int64_t g = P.g;
   const int64_t zb = P.W0 * (int64_t)kRB, ze = P.R1 * (int64_t)kRB;      // rows of the two-term region
   const int Jz = (int)((ze - zb + g - 1) / g);
-  const int j0 = seg * G.L, j1 = min(j0 + G.L, Jz);
+  // (hrb_walk_kernel's formulas: the segments of the wavefronts that took an edge block above are edge_steps shorter)
+  const int j0 = seg * G.L - min(seg, G.edge_segs) * G.edge_steps;
+  const int j1 = min((seg + 1) * G.L - min(seg + 1, G.edge_segs) * G.edge_steps, Jz);
   if (j0 >= j1) return;
   const int dmax = P.near[NN - 1];
   const int64_t coff = (int64_t)col * G.W - dmax;      // first lane's offset inside the strip step

@@ -74,8 +74,7 @@ int64_t padded_block_sum(int64_t nrows, W&& width) {
 // the blocks outside [W0, R1): what a walk leaves to the per-block path
 std::vector<int32_t> edge_blocks(int64_t W0, int64_t R1, int64_t nblocks) {
   std::vector<int32_t> edge;
-  for (int64_t b = 0; b < W0; ++b) edge.push_back((int32_t)b);
-  for (int64_t b = R1; b < nblocks; ++b) edge.push_back((int32_t)b);
+  for (int64_t idx = 0; idx < W0 + (nblocks - R1); ++idx) edge.push_back((int32_t)qp::walk_edge_block(W0, R1, idx));
   return edge;
 }
 

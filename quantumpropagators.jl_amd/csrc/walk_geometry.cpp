@@ -58,24 +58,35 @@ WalkCut walk_cut(const WalkPlan& P, const WalkMatrix& M, const WalkKnobs& k, int
   return C;
 }
 
-Walk2Cut walk2_cut(const WalkPlan& P2, const WalkMatrix& M, const WalkKnobs& k, int cu) {
-  Walk2Cut C;
-  if (!P2.valid || !walk2_shape_supported(P2.nn, P2.K, P2.z0) || P2.xl || P2.fd || P2.g % kRB) return C;
+// what both cuts of the two-term walk share: the chunks of a strip step, the strip steps of the two-term region, the segments the
+// wavefront budget allows (one wavefront per SIMD unless walk_waves says otherwise).  false: no two-term kernel for this plan
+static bool walk2_cut_columns(const WalkPlan& P2, const WalkMatrix& M, const WalkKnobs& k, int cu, Walk2Cut& C) {
+  if (!P2.valid || !walk2_shape_supported(P2.nn, P2.K, P2.z0) || P2.xl || P2.fd || P2.g % kRB) return false;
   Walk2Geom& G = C.G;
   const int dmax = P2.near[P2.nn - 1];
   G.W = kRB - 2 * dmax;
-  if (G.W < 16) return C;
+  if (G.W < 16) return false;
   G.S2 = (int)((P2.g + G.W - 1) / G.W);
   C.Jz = ((P2.R1 - P2.W0) * (int64_t)kRB + P2.g - 1) / P2.g;
   const int64_t waves = k.walk_waves > 0 ? k.walk_waves : (int64_t)kWalk2Waves * cu;   // one per SIMD
   C.nseg_target = std::max<int64_t>(1, waves / G.S2);
-  G.L = (int)((C.Jz + C.nseg_target - 1) / C.nseg_target);
-  G.nseg = (int)((C.Jz + G.L - 1) / G.L);
+  G.xlast = M.ncols - 1;
+  G.vend = (P2.R1 + (int64_t)P2.K * P2.S) * (int64_t)kRB;      // the one-term plan's run end
+  return true;
+}
+static void walk2_cut_grid(Walk2Geom& G) {
   const int64_t ntask = std::max<int64_t>((int64_t)G.nseg * G.S2, 1);
   G.n_walk_wg = (int)((ntask + kWalk2Waves - 1) / kWalk2Waves);
   G.ntask = G.n_walk_wg * kWalk2Waves;
-  G.xlast = M.ncols - 1;
-  G.vend = (P2.R1 + (int64_t)P2.K * P2.S) * (int64_t)kRB;      // the one-term plan's run end
+}
+
+Walk2Cut walk2_cut(const WalkPlan& P2, const WalkMatrix& M, const WalkKnobs& k, int cu) {
+  Walk2Cut C;
+  if (!walk2_cut_columns(P2, M, k, cu, C)) return C;
+  Walk2Geom& G = C.G;
+  G.L = (int)((C.Jz + C.nseg_target - 1) / C.nseg_target);
+  G.nseg = (int)((C.Jz + G.L - 1) / G.L);
+  walk2_cut_grid(G);
   // value loads with the default cache policy once the values are well beyond the Infinity Cache: the chunks overlap by 2 d_max rows and
   // a chunk's packed value halo is its neighbour's stream -- streamed nontemporally, each of those lines comes from memory twice
   // (N = 2^22: 103.6 -> 99.8 us per term, 2^24: 399 -> 363); while most of the values still fit the cache the nontemporal stream
@@ -92,6 +103,47 @@ bool walk2_wanted(const WalkPlan& P1, const WalkPlan& P2, const WalkMatrix& M, c
   if (walk_resident(P2, M)) return false;
   const Walk2Cut C = walk2_cut(P2, M, k, cu);
   return C.taken && C.Jz / C.nseg_target >= 24;
+}
+
+Walk2Cut walk2_cut_resident(const WalkPlan& P2, const WalkMatrix& M, const WalkKnobs& k, int cu) {
+  Walk2Cut C;
+  if (!walk2_cut_columns(P2, M, k, cu, C)) return C;
+  Walk2Geom& G = C.G;
+  // wavefront i < n_edge takes edge block i first (wavefronts of segment i / S2): those segments are shorter -- WalkGeom's balance,
+  // walk_cut's formulas with the two-term region's steps
+  const int dbg_steps = (k.walk_dbg >> kWalkDbgEdgeStepsShift) & 7;
+  G.edge_steps = dbg_steps ? dbg_steps - 1 : kWalk2EdgeSteps;
+  G.edge_segs = G.edge_steps ? (int)std::min<int64_t>(C.nseg_target, (P2.n_edge + G.S2 - 1) / G.S2) : 0;
+  const int64_t J = C.Jz + (int64_t)G.edge_segs * G.edge_steps;
+  G.L = (int)std::max<int64_t>(G.edge_steps + 1, (J + C.nseg_target - 1) / C.nseg_target);
+  G.nseg = (int)((J + G.L - 1) / G.L);
+  while ((int64_t)G.nseg * G.L - (int64_t)std::min(G.edge_segs, G.nseg) * G.edge_steps < C.Jz) ++G.nseg;   // (tiny operators)
+  G.edge_segs = std::min(G.edge_segs, G.nseg);
+  walk2_cut_grid(G);
+  C.ntm = k.walk_nt >= 0 ? k.walk_nt : 0;      // the values stay in the cache from term to term: default policy, as walk_cut
+  C.taken = true;
+  return C;
+}
+
+bool walk2_wanted_resident(const WalkPlan& P1, const WalkPlan& P2, const WalkMatrix& M, const WalkKnobs& k, int cu) {
+  if (!P2.valid || !P1.valid || k.walk_pair == 0 || k.walk_pair == 1) return false;
+  if (P1.R1 - P1.W0 < k.walk_min_blocks) return false;
+  const Walk2Cut C = walk2_cut_resident(P2, M, k, cu);
+  if (k.walk_pair == 2) return C.taken;
+  // not for the real copy of the values: a pair saves half as many bytes there and pays the same run-in and follow-up launch
+  // (N = 2^20: one-term walk 24.7 us per term, resident pair cut 28.3)
+  if (M.real_vals) return false;
+  return walk_resident(P2, M) && C.taken && C.Jz / C.nseg_target >= kWalk2ResidentMinSteps;
+}
+
+Walk2Rule walk2_rule(const WalkPlan& P1, const WalkPlan& P2, const WalkMatrix& M, const WalkKnobs& k, int cu) {
+  if (k.walk_pair == 2) return walk2_wanted_resident(P1, P2, M, k, cu) ? kWalk2Resident : kWalk2None;
+  if (walk2_wanted(P1, P2, M, k, cu)) return kWalk2Streamed;
+  return kWalk2ResidentAuto && walk2_wanted_resident(P1, P2, M, k, cu) ? kWalk2Resident : kWalk2None;
+}
+
+Walk2Cut walk2_cut_of(Walk2Rule rule, const WalkPlan& P2, const WalkMatrix& M, const WalkKnobs& k, int cu) {
+  return rule == kWalk2Resident ? walk2_cut_resident(P2, M, k, cu) : rule == kWalk2Streamed ? walk2_cut(P2, M, k, cu) : Walk2Cut();
 }
 
 }  // namespace qp

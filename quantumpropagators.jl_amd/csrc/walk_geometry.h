@@ -42,6 +42,10 @@ struct WalkPlan {
   int64_t n_edge = 0;
 };
 
+// entry `idx` of a plan's edge list (operator_plans.cpp builds edge_map from this): the blocks below W0, then those from R1 on.
+// (constexpr: host and device code alike)
+constexpr int64_t walk_edge_block(int64_t W0, int64_t R1, int64_t idx) { return idx < W0 ? idx : R1 + (idx - W0); }
+
 // is there a strip-walk kernel instance for this stencil shape?  (The dispatch of kernels_walk_impl.h: launch_shape instantiates
 // exactly these; inline here so that the host planners -- and their sanitizer build, tests/sanitize_host_index.cpp -- see the same list.)
 // near distances 1..4 of at most 16 rows, far reach 1..4 strip steps, with or without a diagonal
@@ -85,6 +89,10 @@ struct Walk2Geom {
   int W = 0;           // rows of a chunk that form z: 64 - 2 d_max
   int64_t xlast = 0;   // last element of x
   int64_t vend = 0;    // first row beyond the lattice run (values at the run's strides exist below it)
+  // the one-term walk's balance (WalkGeom): wavefront i < n_edge takes edge block i before its walk, and segments
+  // 0 .. edge_segs - 1 -- theirs -- are `edge_steps` steps shorter.  0: every segment has L steps (walk2_cut)
+  int edge_segs = 0;
+  int edge_steps = 0;
 };
 
 constexpr int kWalkWaves = 8;       // most wavefronts (adjacent strip columns) per workgroup; the launch may use fewer (knob walk_wg)
@@ -128,9 +136,38 @@ struct Walk2Cut {
 };
 Walk2Cut walk2_cut(const WalkPlan& P2, const WalkMatrix& M, const WalkKnobs& k, int cu);
 
-// Does a whole-operator cheby! take the two-term walk of `P2` (P1: the operator's one-term plan)?  Beyond the Infinity Cache only
-// (inside it the one-term walk is not bound by the value stream), and only when a wavefront's strip column is long enough for
+// Does a whole-operator cheby! take the two-term walk of `P2` (P1: the operator's one-term plan) with walk2_cut?  Beyond the Infinity
+// Cache only (inside it: walk2_wanted_resident below), and only when a wavefront's strip column is long enough for
 // the 2 K steps a segment runs in before its first z to be a small part of it.
 bool walk2_wanted(const WalkPlan& P1, const WalkPlan& P2, const WalkMatrix& M, const WalkKnobs& k, int cu);
+
+// ---- the two-term walk of an operator INSIDE the Infinity Cache -------------------------------------------------------
+// What a pair costs there beyond its value stream is the run-in (2 K steps per segment) and the edge blocks its wavefronts take
+// first.  So the cut gives the wavefronts with an edge block shorter segments (Walk2Geom::edge_segs / edge_steps), and the value
+// loads keep the default cache policy.  Measured at N = 2^20 (profiles/walk2_resident.txt), us per term.  Against each other, in
+// regions of 20 steps: one wavefront per SIMD 30.9, 760 wavefronts 34.5, 608 38.7 (fewer only lengthen the launch); edge_steps
+// 0 / 2 / 3 / 4: 31.9 / 31.3 / 30.9 / 31.5; nontemporal values 34.5; walk2_cut with its nontemporal values 35.4.  Against the
+// one-term walk, in regions of 60 steps (the figures that agree with bench.py's 100): 29.9 against 30.75 (the short regions give the
+// pair about 1 us more and the one-term walk 0.2 less; why is not known).  The real copy of the values: 28.3 against 24.7 -- not taken.
+constexpr int kWalk2EdgeSteps = 3;           // steps a segment with an edge block is shorter
+constexpr bool kWalk2ResidentAuto = true;    // the automatic rule (walk_pair = -1) takes walk2_wanted_resident's verdict (bench.py: + 5.9 %)
+// automatic rule: a wavefront's share of the strip column, at least.  Measured at ONE point only -- 19 steps, the (4, 4) lattice at
+// N = 2^20, 2 K = 8 of run-in; nothing between 4 (2^18) and 19 steps and no other shape was measured: 16 keeps the rule to what was
+constexpr int kWalk2ResidentMinSteps = 16;
+// knob walk_dbg (measurements only), beyond the one-term walk's bits 1, 2, 4:
+constexpr int kWalkDbgPairFollowUpPerBlock = 8;   // term m + 1 of a pair's edge blocks by the per-block kernel (row set) instead of hrb_walk2_edge_kernel
+constexpr int kWalkDbgEdgeStepsShift = 4;         // bits 16 | 32 | 64 = n > 0: walk2_cut_resident with edge_steps = n - 1
+Walk2Cut walk2_cut_resident(const WalkPlan& P2, const WalkMatrix& M, const WalkKnobs& k, int cu);
+// The automatic rule inside the cache: the operator is resident, its values are complex (M.real_vals: measured, a loss), its shape
+// has a pair kernel, and a wavefront's segment is at
+// least kWalk2ResidentMinSteps long (the headline lattice at N = 2^20 on 256 compute units: 19; at 2^16: 1).  walk_pair = 2
+// forces it at any size; 0 and 1 never take it.
+bool walk2_wanted_resident(const WalkPlan& P1, const WalkPlan& P2, const WalkMatrix& M, const WalkKnobs& k, int cu);
+
+// Which cut a whole-operator cheby! takes its pairs with -- kWalk2None: one-term launches; kWalk2Streamed: walk2_cut (walk2_wanted,
+// walk_pair = 1); kWalk2Resident: walk2_cut_resident (walk2_wanted_resident, walk_pair = 2) -- and that cut
+enum Walk2Rule { kWalk2None = 0, kWalk2Streamed = 1, kWalk2Resident = 2 };
+Walk2Rule walk2_rule(const WalkPlan& P1, const WalkPlan& P2, const WalkMatrix& M, const WalkKnobs& k, int cu);
+Walk2Cut walk2_cut_of(Walk2Rule rule, const WalkPlan& P2, const WalkMatrix& M, const WalkKnobs& k, int cu);
 
 }  // namespace qp
