@@ -29,18 +29,17 @@
 // term m + 1 from a launch over the same list afterwards (kernels_walk2.hip: hrb_walk2_edge_kernel; engine_cheby.hip).
 //
 // Both row sums are the one-term walk's (lower slots then upper slots in storage order, two interleaved partial sums) and both
-// epilogues are ChebyOp's: bit-identical to one-term launches (tests/test_gpu_walk2.py).
+// epilogues are ChebyOp's: bit-identical to one-term launches (tests/test_gpu_walk2.py).  The step is a written-out copy per phase
+// (walk_step.h says what is shared as code and why not more); tests/test_gpu_walk2_forms.py holds every instance to the order.
 #pragma once
 #include "kernels_walk_impl.h"
 
 namespace qp {
 
 template <int NN, int K>
-struct Walk2Lds {
-  static constexpr int XW = kRB + 2 * kWalkHalo, AW = kRB + kWalkHalo;
-  static constexpr int kWin = XW + NN * AW;                    // the near windows (phase Y, then phase Z)
+struct Walk2Lds : WalkWindows<NN> {                            // the near windows (phase Y, then phase Z), then the FIFOs
   static constexpr int kFifo = K * K + K * (K + 1) / 2;        // far slot m: K + m entries of 64
-  static constexpr int kPerWave = kWin + kRB * kFifo;
+  static constexpr int kPerWave = WalkWindows<NN>::kWin + kRB * kFifo;
   static constexpr size_t kBytesPerWave = sizeof(double2) * (size_t)kPerWave;
 };
 
@@ -87,9 +86,7 @@ __global__ __launch_bounds__(64 * kWalk2Waves) void hrb_walk2_kernel(const VT* _
   double2* __restrict__ xwin = walk2_lds + (size_t)wave * Lds::kPerWave;
   double2* __restrict__ fifo = xwin + Lds::kWin;
   const int64_t rlo = P.R0 * (int64_t)kRB, vmax = G.vend - 1, rmax = G.xlast, nlast = nrows - 1;
-  auto vpos = [&](int64_t r) __attribute__((always_inline)) -> int64_t {
-    return P.U0 + ((r >> 6) - P.R0) * (int64_t)P.ustride + (r & 63);
-  };
+  auto vpos = [&](int64_t r) __attribute__((always_inline)) -> int64_t { return walk_vpos(P, r); };
   auto clampv = [&](int64_t r) __attribute__((always_inline)) -> int64_t { return min(max(r, rlo), vmax); };
   ChebyOp opl1{op1.e}, opl2{op2.e};
   opl1.e.mirror = opl2.e.mirror = nullptr;

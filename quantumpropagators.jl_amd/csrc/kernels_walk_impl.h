@@ -18,12 +18,15 @@
 // nearly all of them HBM streams, requested one step ahead.  N = 2^22: 174 -> 126 us per term (0.56 -> 0.79 of 8 TB/s).
 //
 // Summation order per row is that of the per-block kernel (lower slots then upper slots in storage order, two
-// interleaved partial sums), so the two kernels agree bit for bit (tests/test_gpu_parity.py).
+// interleaved partial sums), so the two kernels agree bit for bit (tests/test_gpu_parity.py).  The two-term walk
+// (kernels_walk2_impl.h) runs this step too, written out again in both of its phases; walk_step.h holds what the two share as code
+// and says why the step itself is not in it.
 #pragma once
 #include <atomic>
 #include <type_traits>
 
 #include "kernel_common.h"
+#include "walk_step.h"
 
 namespace qp {
 
@@ -237,13 +240,11 @@ __device__ __forceinline__ double2 lane_shift2(double2 v, double2 edge, int lane
   return make_double2(e ? edge.x : t.x, e ? edge.y : t.y);
 }
 
-// LDS of one wavefront, in double2 elements: the near window of x (16 + 64 + 16), NN near value windows (16 + 64) and the
-// FIFOs of the far upper values (slot m: m entries of 64; with diagonal far neighbours, FD = 1, three slots per m)
+// LDS of one wavefront, in double2 elements: the near windows (walk_step.h) and behind them the FIFOs of the far upper values
+// (slot m: m entries of 64; with diagonal far neighbours, FD = 1, three slots per m)
 template <int NN, int K, int FD = 0>
-struct WalkLds {
-  static constexpr int XW = kRB + 2 * kWalkHalo, AW = kRB + kWalkHalo;
-  static constexpr int kHist = XW + NN * AW;
-  static constexpr int kPerWave = kHist + kRB * (1 + 2 * FD) * (K * (K + 1) / 2);
+struct WalkLds : WalkWindows<NN> {
+  static constexpr int kPerWave = WalkWindows<NN>::kWin + kRB * (1 + 2 * FD) * (K * (K + 1) / 2);
   static constexpr size_t kBytesPerWave = sizeof(double2) * (size_t)kPerWave;
 };
 
@@ -324,11 +325,8 @@ __global__ __launch_bounds__(64 * kWalkWaves) void hrb_walk_kernel(const VT* __r
   if (seg < G.nseg && j0 < j1) {
   const int dmax = P.near[NN - 1];
   double2* __restrict__ xwin = walk_lds + (size_t)wave * Lds::kPerWave;
-  double2* __restrict__ hring = xwin + Lds::kHist;
-  // position of slot 0 of row r in the upper value array (r inside the run; rows of one 64-row block are contiguous)
-  auto vpos = [&](int64_t r) __attribute__((always_inline)) -> int64_t {
-    return P.U0 + ((r >> 6) - P.R0) * (int64_t)P.ustride + (r & 63);
-  };
+  double2* __restrict__ hring = xwin + Lds::kWin;
+  auto vpos = [&](int64_t r) __attribute__((always_inline)) -> int64_t { return walk_vpos(P, r); };
   const int64_t rmax = G.xlast;
   const int64_t vmax = P.R1 * (int64_t)kRB - 1;               // last row whose values sit at the run's strides
   // No branch inside the walk: a join in the control flow makes the compiler wait for EVERY outstanding load (the

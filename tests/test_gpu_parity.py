@@ -3,6 +3,7 @@ the same seeded inputs.  Tolerance for complex-fp64 results is ||delta psi||_2 <
 (BASELINE.json north_star; the reference's own bar in test/test_cheby.jl:47 and
 test/test_newton.jl:65,125,175); index work is bit-exact."""
 import os
+import re
 import sys
 
 import numpy as np
@@ -964,13 +965,34 @@ def test_strip_walk_long_pair_three_dimensional_grids(ctx, dims, flux, uniform):
     assert np.linalg.norm(base - ref) < TOL
 
 
+def _uniform_shape(case):
+    """`uniform_n<near>k<far>z<diag>x<long pairs>[_fd][_real]`: the offsets of a translation-invariant lattice of that walk shape
+    (strip step 128 rows, N = 2^15) and what walk_info() must say.  With these every kernel instance of the long-pair and
+    diagonal-neighbour families is run, complex values and real copy (profiles/walk_step_core.txt lists which case reaches which)."""
+    nn, K, z0, xl = (int(t) for t in re.fullmatch(r"uniform_n(\d+)k(\d+)z(\d+)x(\d+)(_fd)?(_real)?", case).groups()[:4])
+    fd = "_fd" in case
+    near = {1: (2,), 2: (1, 2)}[nn] if fd else {1: (1,), 2: (1, 3)}[nn]
+    far = (127, 128, 129) if fd else tuple(128 * m for m in range(1, K + 1))
+    longs = {0: (), 1: (2500,), 2: (1111, 2222)}[xl]
+    return near + far + longs, dict(near=nn, far=K, diag=z0, longs=list(longs), step=128, fd=int(fd))
+
+
+# (near, far, diag, long pairs) of the sixteen long-pair kernel shapes that the named cases leave out, complex values and real copy
+XL_SHAPE_CASES = (["uniform_n%dk%dz%dx%d" % s for s in ((1, 1, 0, 1), (2, 1, 0, 1), (1, 2, 0, 1), (1, 2, 1, 1), (2, 2, 0, 1), (1, 1, 0, 2),
+                                                        (2, 1, 0, 2), (2, 1, 1, 2), (1, 2, 0, 2), (1, 2, 1, 2))] +
+                  ["uniform_n%dk%dz%dx%d_real" % s for s in ((1, 1, 0, 1), (2, 1, 0, 1), (2, 1, 1, 1), (1, 2, 0, 1), (1, 2, 1, 1), (2, 2, 0, 1),
+                                                             (2, 2, 1, 1), (1, 1, 0, 2), (1, 1, 1, 2), (2, 1, 0, 2), (2, 1, 1, 2), (1, 2, 0, 2),
+                                                             (1, 2, 1, 2), (2, 2, 0, 2))])
+
+
 @pytest.mark.parametrize("case", ["grid_4th_order_72x10x20", "grid_4th_order_real_64x8x24", "uniform_k1_two_pairs", "uniform_k2_one_pair",
-                                  "uniform_k2_two_pairs_no_diag"])
+                                  "uniform_k2_two_pairs_no_diag"] + XL_SHAPE_CASES)
 def test_strip_walk_two_long_pairs_and_two_far_distances(ctx, case):
     """The long-pair shapes beyond (one pair, one far distance): the fourth-order Laplacian of an open-boundary nx x ny x nz grid
     -- distances +-1, +-2, +-nx, +-2 nx, +-nx ny, +-2 nx ny: near 2, far 2, TWO long pairs, completed at creation like the
     seven-point one -- and translation-invariant lattices with one / two far distances and one / two pairs.  Bit-identical to
-    the per-block kernel for several partitions of the walk, within 1e-10 of the oracle."""
+    the per-block kernel for several partitions of the walk, within 1e-10 of the oracle.  The uniform_n.k.z.x. cases (_uniform_shape)
+    are the remaining long-pair shapes, one pair and one far distance included."""
     if case.startswith("grid"):
         dims = (72, 10, 20) if "72x10x20" in case else (64, 8, 24)     # (nx >= 64: the strip step)
         H = synth.grid_hamiltonian_3d(*dims, flux=0.0 if "real" in case else 0.15, order=4)
@@ -979,10 +1001,13 @@ def test_strip_walk_two_long_pairs_and_two_far_distances(ctx, case):
         want = dict(near=2, far=2, diag=1, longs=[dims[0] * dims[1], 2 * dims[0] * dims[1]], step=dims[0])
     else:
         N = 1 << 15
-        offs, want = {"uniform_k1_two_pairs": ((1, 128, 1000, 3001), dict(near=1, far=1, diag=1, longs=[1000, 3001], step=128)),
-                      "uniform_k2_one_pair": ((1, 3, 100, 200, 2500), dict(near=2, far=2, diag=1, longs=[2500], step=100)),
-                      "uniform_k2_two_pairs_no_diag": ((2, 5, 192, 384, 1111, 2222), dict(near=2, far=2, diag=0, longs=[1111, 2222], step=192))}[case]
+        offs, want = _uniform_shape(case) if case.startswith("uniform_n") else {
+            "uniform_k1_two_pairs": ((1, 128, 1000, 3001), dict(near=1, far=1, diag=1, longs=[1000, 3001], step=128)),
+            "uniform_k2_one_pair": ((1, 3, 100, 200, 2500), dict(near=2, far=2, diag=1, longs=[2500], step=100)),
+            "uniform_k2_two_pairs_no_diag": ((2, 5, 192, 384, 1111, 2222), dict(near=2, far=2, diag=0, longs=[1111, 2222], step=192))}[case]
         rp, col, vals = synth.hermitian_offsets_csr(N, offsets=offs)
+        if "real" in case:
+            vals = vals.real.astype(np.complex128)
         H = synth.to_scipy(rp, col, vals, N)
         if want["diag"]:
             H = sp.csr_matrix(H + sp.diags(np.linspace(-1.0, 1.0, N)).astype(np.complex128))
@@ -997,6 +1022,7 @@ def test_strip_walk_two_long_pairs_and_two_far_distances(ctx, case):
         wi = Op.walk_info()
         assert wi["valid"] == 1 and (wi["near"], wi["far"], wi["diag"]) == (want["near"], want["far"], want["diag"])
         assert wi["long_distances"] == want["longs"] and wi["long_distance"] == want["longs"][-1] and wi["rows_per_step"] == want["step"]
+        assert wi["far_diagonals"] == 0
         if case.startswith("grid"):
             assert Op.fill_info() > 0 and wi["first_block"] >= want["longs"][-1] // 64
         wrk = L.ChebyWrk(ctx, N, Delta, Emin, 0.6)
@@ -1023,8 +1049,13 @@ def test_strip_walk_two_long_pairs_and_two_far_distances(ctx, case):
     assert np.linalg.norm(base - ref) < TOL
 
 
+# (near, diag, long pairs) of the eight diagonal-neighbour kernel shapes that the named cases leave out (far = 1 always)
+FD_SHAPE_CASES = (["uniform_n%dk1z%dx%d_fd" % s for s in ((2, 0, 0), (2, 1, 0), (1, 0, 1), (2, 0, 1), (2, 1, 1))] +
+                  ["uniform_n%dk1z%dx%d_fd_real" % s for s in ((1, 0, 0), (2, 0, 0), (1, 0, 1), (1, 1, 1), (2, 0, 1), (2, 1, 1))])
+
+
 @pytest.mark.parametrize("case", ["uniform_256", "uniform_100_no_diag", "uniform_real_two_near", "grid_96x50_tprime", "grid_128x40_tprime_real",
-                                  "uniform_128_long_pair", "layers_72x10x20_tprime"])
+                                  "uniform_128_long_pair", "layers_72x10x20_tprime"] + FD_SHAPE_CASES)
 def test_strip_walk_diagonal_far_neighbours(ctx, case):
     """Far distances with their diagonal neighbours, g - 1, g, g + 1 (nine-point stencil: next-nearest hopping on a two-dimensional
     grid): the gathered elements are the ring's elements one lane over (a DPP wavefront shift, the edge lane from a packed halo
@@ -1043,7 +1074,8 @@ def test_strip_walk_diagonal_far_neighbours(ctx, case):
         want = dict(near=1, diag=1, step=nx)
     else:
         N = 1 << 15
-        offs, want = {"uniform_256": ((1, 255, 256, 257), dict(near=1, diag=1, step=256)),
+        offs, want = _uniform_shape(case) if case.startswith("uniform_n") else {
+                      "uniform_256": ((1, 255, 256, 257), dict(near=1, diag=1, step=256)),
                       "uniform_128_long_pair": ((2, 127, 128, 129, 3001), dict(near=1, diag=1, step=128, long=3001)),
                       "uniform_100_no_diag": ((3, 99, 100, 101), dict(near=1, diag=0, step=100)),
                       "uniform_real_two_near": ((1, 2, 511, 512, 513), dict(near=2, diag=1, step=512))}[case]
@@ -1064,7 +1096,7 @@ def test_strip_walk_diagonal_far_neighbours(ctx, case):
         wi = Op.walk_info()
         assert wi["valid"] == 1 and wi["far_diagonals"] == 1 and wi["far"] == 1
         assert (wi["near"], wi["diag"], wi["rows_per_step"]) == (want["near"], want["diag"], want["step"])
-        assert wi["long_distances"] == ([want["long"]] if "long" in want else [])
+        assert wi["long_distances"] == want.get("longs", [want["long"]] if "long" in want else [])
         if case.startswith("grid") or case.startswith("layers"):
             assert Op.fill_info() > 0
         wrk = L.ChebyWrk(ctx, N, Delta, Emin, 0.6)
